@@ -15,6 +15,8 @@ predict(z = electrodes, t, type="csd") of every resident trial, inputs resident 
     python bench.py --workload cfg5          # GPCSD1D fit: restarts evaluated in lock-step batches (BASELINE configs[4])
     python bench.py --only-value             # setup + warm-up + timed loop and nothing else: the command the rocprofv3 kernel
                                              # stats / PMC passes under profiles/ are taken over (tools/profile_r06.sh)
+    python bench.py --dump-outputs DIR       # also write what the timed loop's last step returned as DIR/<name>.npy (seeded
+                                             # inputs, the same on every run: two builds compare output for output)
 The default cfg3 line at N=1 also carries compact cfg2 / cfg3fit / cfg5 / npx69 / aud24 / potrf sub-results (each a child process of
 its own) so that the driver's record holds them; --no-sub-results skips them.  The measuring code lives in benchlib/ (workloads,
 step, fit, cpu, profiles, line); this file is the contract: CLI, rank launch, sub-results, the printed line.
@@ -37,11 +39,6 @@ import json
 import os
 import sys
 import time
-
-# A context keeps four streams busy; torch's side stream and RCCL's own bring more.  The HIP runtime multiplexes
-# streams onto 4 hardware queues by default, and streams that share one serialise: the 8-byte all-reduce of a multi-rank step
-# then waits behind a whole predict tail (3.7 instead of 1.94 ms per step).  Must be set before the runtime initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 import numpy as np
 
@@ -119,7 +116,14 @@ def main():
     ap.add_argument("--n1-value", type=float, default=None,
                     help="N > 1: the N = 1 `value` of this workload (trials/s) to quote scaling_efficiency against; without it the "
                          "efficiency is quoted against the ranks' own rates without collectives, measured in the same processes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed loop's last step returned as DIR/<name>.npy (float64, "
+                         "at most %d bytes in all: past that, a fixed seeded sample of each array's elements)" % DUMP_LIMIT_BYTES)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs is not None and args.workload == "potrf":
+        ap.error("--dump-outputs: the potrf workload has no step loop")
 
     # `python bench.py --gpus N` (no launcher): start the N ranks ourselves.  This process has not touched the GPU (torch is not
     # even imported yet) and never will: the ranks are a fresh `torch.distributed.run` child, whose rank 0 prints the line.
@@ -177,10 +181,11 @@ def main():
     # 1.12 ms per step for 0.86: its sub-result ran after the CPU baseline, whose OpenBLAS workers were still spinning on the CPUs
     # the launch thread is bound to.)
     cpu_legs = []
+    outputs = {} if args.dump_outputs is not None else None
     if args.workload in FIT_WORKLOADS:
-        out = run_fit_bench(args, w, rank, world, local_rank, backend, cpu_legs=cpu_legs)
+        out = run_fit_bench(args, w, rank, world, local_rank, backend, cpu_legs=cpu_legs, outputs=outputs)
     else:
-        out = run_step_bench(args, w, rank, world, local_rank, backend, cpu_legs=cpu_legs)
+        out = run_step_bench(args, w, rank, world, local_rank, backend, cpu_legs=cpu_legs, outputs=outputs)
     # the driver runs `bench.py --gpus 1` only: carry compact cfg2 / cfg5 / potrf / npx69 / aud24 results with that run (N=1, a few
     # seconds each); their headline scalars go into `config` of the line, the full dicts into the detail file
     sub = None
@@ -195,6 +200,8 @@ def main():
     if rank == 0 and out is not None:
         out["host_affinity"] = ({"bound_to_numa_node": host_numa["node"], "cpus": host_numa["cpus"], "device_pci": host_numa["pci"]}
                                 if host_numa else {"bound_to_numa_node": None, "cpus": len(os.sched_getaffinity(0))})
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         emit(out)
     if world > 1 or force_dist:                       # the line is out; leave the communicator the orderly way (no exit-time warning)
         import torch.distributed as td
@@ -218,6 +225,27 @@ def emit(full):
                 print("bench.py: could not write %s: %s" % (os.path.join(d, DETAIL_FILE), e), file=sys.stderr)
     sys.stdout.flush()
     print(compact_record(full), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirpath, arrays, seed=0):
+    """Write each array as <dirpath>/<name>.npy in float64.  When they hold more than DUMP_LIMIT_BYTES in all, every array of
+    more than one element is replaced by a fixed, seeded sample of its elements (flat C-order indices, ascending) that takes its
+    share of the limit: the same arguments give the same sample, so that two builds can be compared element for element."""
+    os.makedirs(dirpath, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    room = DUMP_LIMIT_BYTES - 1024 * len(arrays)          # (an .npy header is a few hundred bytes)
+    for name, a in arrays.items():
+        what = "shape %s" % (a.shape,)
+        if total > room and a.size > 1:
+            keep = a.size * room // total
+            a = a.reshape(-1)[np.sort(np.random.RandomState(seed).choice(a.size, keep, replace=False))]
+            what = "%d seeded samples of %s" % (keep, what)
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+        print("bench.py: wrote %s.npy (%s)" % (os.path.join(dirpath, name), what), file=sys.stderr)
 
 
 SUB_RESULT_KEYS = ("cfg2", "cfg3fit", "cfg5", "npx69", "aud24", "potrf")

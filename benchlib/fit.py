@@ -55,7 +55,7 @@ def _quiesce_host(seconds=0.25):
     time.sleep(seconds)
 
 
-def run_fit_bench(args, w, rank, world, local_rank, backend, compact=False, cpu_legs=None):
+def run_fit_bench(args, w, rank, world, local_rank, backend, compact=False, cpu_legs=None, outputs=None):
     """BASELINE cfg5: GPCSD1D hyper-parameter fit, 24 x 500 x 200 trials resident on every GPU, 32 restarts sharded over the
     GPUs.  The unit of work is one objective + analytic-gradient evaluation of one restart (what L-BFGS-B asks for); a step
     evaluates one lock-step batch of B restarts in one chain of launches (gpcsd_loglik_grad_batch).  Reported: evaluations/s
@@ -120,14 +120,19 @@ def run_fit_bench(args, w, rank, world, local_rank, backend, compact=False, cpu_
         group_hps.append([h for h, _ in gh])
         sets.extend(gh)                                          # keep the sig2n arrays alive
 
+    last = [None] * G                                            # each group's result of the latest step
+
     def run_groups(nsteps):
         if G == 1:
             for _ in range(nsteps):
-                ctx.loglik_grad_batch(hps, ng)
+                last[0] = ctx.loglik_grad_batch(hps, ng)
             return
         import threading
-        ths = [threading.Thread(target=lambda c=c, h=h: [c.loglik_grad_batch(h, ng) for _ in range(nsteps)])
-               for c, h in zip(ctxs, group_hps)]
+
+        def group(gi):
+            for _ in range(nsteps):
+                last[gi] = ctxs[gi].loglik_grad_batch(group_hps[gi], ng)
+        ths = [threading.Thread(target=group, args=(gi,)) for gi in range(G)]
         for th in ths:
             th.start()
         for th in ths:
@@ -144,6 +149,9 @@ def run_fit_bench(args, w, rank, world, local_rank, backend, compact=False, cpu_
         cg.synchronize()
     fence()
     elapsed = time.perf_counter() - t0
+    if outputs is not None:                # what the timed loop's last step returned, groups one after the other
+        for i, name in enumerate(("sumlog", "quad", "grad")):
+            outputs[name] = np.concatenate([r[i] for r in last])
     if args.only_value:                    # the command the rocprofv3 passes under profiles/ are taken over: nothing after the loop
         if rank != 0:
             return None

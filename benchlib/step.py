@@ -14,7 +14,7 @@ from .workloads import (FP64_MFMA_SPEC_TFLOPS, HBM_PEAK_GBS, N_CUS, SETTLE_S, al
                         synth_data)
 
 
-def run_step_bench(args, w, rank, world, local_rank, backend, compact=False, cpu_legs=None):
+def run_step_bench(args, w, rank, world, local_rank, backend, compact=False, cpu_legs=None, outputs=None):
     import torch
     from gpcsd_amd import _hip
     from gpcsd_amd.dist import TrialSharding
@@ -138,6 +138,13 @@ def run_step_bench(args, w, rank, world, local_rank, backend, compact=False, cpu
     elapsed = time.perf_counter() - t0
     if sharding is not None:
         ll = state["ll"]                          # the last step's global log-likelihood, collected inside the timed region
+    if outputs is not None:
+        # what the timed loop's last step hands its caller (this rank's trials), fetched before anything else is queued: the
+        # log-likelihood and the prediction it left in HBM, as predict() would return it (csd_pred, csd_pred_list)
+        shape = (z.shape[0], w["nt"], R_local)
+        outputs["loglik"] = np.array([float(ll)])
+        outputs["csd_pred"] = ctx.fetch("pred_out_csd", shape).copy()
+        outputs["csd_pred_list"] = ctx.fetch("pred_out_csd_list", (C,) + shape).copy()
     dist_info = None
     if sharding is not None:
         import torch.distributed as td

@@ -18,8 +18,7 @@ for ev in none malloc mallocfree manysmall hostalloc hostallocfree numpy newctx 
 done
 PROBE_HEARTBEAT=1 step 120 inj_graphs_hb.txt python tools/stall_inject.py graphs
 grep -h '^{\|HEARTBEAT' $OUT/inj_graphs_hb.txt | cut -c1-900
-GPU_MAX_HW_QUEUES=4 step 200 probe_hwq4.txt python tools/stall_probe.py cfg2 8
-for f in probe_base probe_settle probe_hwq4; do python3 - $OUT/$f.txt <<'PY'
+for f in probe_base probe_settle; do python3 - $OUT/$f.txt <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(sys.argv[1].split('/')[-1], "stalled", d["stalled_loops"], [(l["max_ms"], l["stall_s_after_first_evaluation"], l["untimed_stalls_s_after_first_evaluation"]) for l in d["loops"]])

@@ -25,8 +25,8 @@ for rep in 1 2; do
   done
 done
 step 200 t_recipe.txt python -m pytest -x -q -s -m gpu tests/test_recipe.py tests/test_resident_predictions.py -p no:cacheprovider; tail -4 $OUT/t_recipe.txt
-step 200 probe_two_ctx.txt python tools/stall_probe.py cfg3 4; GPU_MAX_HW_QUEUES=16 step 200 probe_two_ctx_hwq16.txt python tools/stall_probe.py cfg3 4
-for f in probe_two_ctx probe_two_ctx_hwq16; do python3 - $OUT/$f.txt <<'PY'
+step 200 probe_two_ctx.txt python tools/stall_probe.py cfg3 4
+for f in probe_two_ctx; do python3 - $OUT/$f.txt <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(sys.argv[1].split('/')[-1], [l["median_ms"] for l in d["loops"]])
