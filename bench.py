@@ -5,7 +5,7 @@ Default workload (BASELINE.json configs[2]/[3]): GPCSD2D, 384-ch
 points, 50 synthetic trials PER GPU (cfg3 at N=1; cfg4 = 400 trials at N=8: weak scaling), float64, ngl 20x60,
 SE + Matern-1/2 temporal kernels.  One step = one loglik() evaluation over the resident trials + one
 predict(z = electrodes, t, type="csd") of every resident trial, inputs resident in HBM, outputs left in HBM
-(no PCIe in the timed region; the PCIe-inclusive rate of the class-API predict() is reported separately).
+(no PCIe in the timed region; the PCIe-inclusive rate of the class-API predict() is reported separately with --full).
 
     python bench.py --gpus 1 --steps 100 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -13,15 +13,24 @@ predict(z = electrodes, t, type="csd") of every resident trial, inputs resident 
     python bench.py --workload cfg2          # GPCSD1D 24 x 500 x 200 trials (BASELINE configs[1]), same step
     python bench.py --workload cfg3fit       # GPCSD2D.fit() at the headline geometry: objective + analytic gradient evaluations
     python bench.py --workload cfg5          # GPCSD1D fit: restarts evaluated in lock-step batches (BASELINE configs[4])
-    python bench.py --only-value             # setup + warm-up + timed loop and nothing else: the command the rocprofv3 kernel
-                                             # stats / PMC passes under profiles/ are taken over (tools/profile_r06.sh)
     python bench.py --dump-outputs DIR       # also write what the timed loop's last step returned as DIR/<name>.npy (seeded
                                              # inputs, the same on every run: two builds compare output for output)
-The default cfg3 line at N=1 also carries compact cfg2 / cfg3fit / cfg5 / npx69 / aud24 / potrf sub-results (each a child process of
-its own) so that the driver's record holds them; --no-sub-results skips them.  The measuring code lives in benchlib/ (workloads,
-step, fit, cpu, profiles, line); this file is the contract: CLI, rank launch, sub-results, the printed line.
+    python bench.py --full                   # everything below as well
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints the line: value, ms_per_step and
+the configuration, nothing measured beside them.  It is the command the rocprofv3 kernel stats / PMC passes under profiles/ are
+taken over (tools/profile_r06.sh; --only-value, which those commands pass, means the same).
+
+--full adds, after the timed loop: the halves of the step as fenced calls, the step without announcements and with the library's
+defaults, two steps in flight, the decomposition cache, the class-API predict() with its PCIe copy, the roofline passes, the
+oracle parity spot check and the CPU baseline (or, for the fit workloads: one group alone, one evaluation at a time, batch sizes,
+a truncated real fit(), parity and the CPU baseline); at N > 1 the ranks' own rates without collectives.  The cfg3 line at N=1
+then also carries compact cfg2 / cfg3fit / cfg5 / npx69 / aud24 / potrf sub-results (each a child process of its own);
+--no-sub-results skips them.  The measuring code lives in benchlib/ (workloads, step, fit, cpu, profiles, line); this file is
+the contract: CLI, rank launch, sub-results, the printed line.
 
 Rank 0 prints ONE JSON line.
+  setup_steps   untimed steady-state setup evaluations in front of the W warm-up steps (graph capture, clocks).
+With --full it also holds:
   roofline      step level, as SURVEY 8(d) specifies: flops per step / ms_per_step against the fp64 MFMA peak, once in flops
                 actually launched (folded basis, symmetry-folded eigensolver) and once in flops of the reference's algorithm;
                 beside it the kernel with the largest share of GPU time (the single-workgroup tridiagonalisation tail) with
@@ -32,7 +41,6 @@ Rank 0 prints ONE JSON line.
   cpu_baseline  the NumPy oracle (a port: the Python reference cannot travel to the GPU box) on the SAME number of trials
                 as the GPU step, BLAS threads swept, >= 20 loglik / >= 3 predict repetitions at the best setting, plus the
                 single-thread figure and the reference's strided per-trial layout priced next to the contiguous one.
-  setup_steps   untimed steady-state setup evaluations in front of the W warm-up steps (graph capture, clocks).
 """
 import argparse
 import json
@@ -101,10 +109,12 @@ def main():
     ap.add_argument("--workload", default="cfg3")
     ap.add_argument("--trials-per-gpu", type=int, default=None)
     ap.add_argument("--setup-steps", type=int, default=150)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed loop, also measure and check everything beside the headline (see the module docstring)")
     ap.add_argument("--only-value", action="store_true",
-                    help="setup + warm-up + timed loop, then print value / ms_per_step and exit: the command profiled under profiles/")
-    ap.add_argument("--no-sub-results", action="store_true", help="skip the compact cfg2 / cfg5 sub-results of the default line")
+                    help="the plain run (no --full): the command profiled under profiles/, which passes this flag")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-sub-results", action="store_true", help="--full: skip the compact sub-results of the cfg3 line")
     ap.add_argument("--sub-result", default=None, choices=SUB_RESULT_KEYS,
                     help="measure one sub-result of the default line and print its dict (what the default run starts as a child)")
     ap.add_argument("--cpu-budget-s", type=float, default=45.0)
@@ -114,8 +124,8 @@ def main():
                     help="cfg5: lock-step groups running side by side on one GPU, each on its own context and host thread "
                          "(measured: one large batch beats several groups -- 7.5 k evals/s at 1 x 32 against 6.3 k at 2 x 16)")
     ap.add_argument("--n1-value", type=float, default=None,
-                    help="N > 1: the N = 1 `value` of this workload (trials/s) to quote scaling_efficiency against; without it the "
-                         "efficiency is quoted against the ranks' own rates without collectives, measured in the same processes")
+                    help="N > 1: the N = 1 `value` of this workload (trials/s) to quote scaling_efficiency against; without it, "
+                         "--full quotes the efficiency against the ranks' own rates without collectives, measured in the same processes")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed loop's last step returned as DIR/<name>.npy (float64, "
                          "at most %d bytes in all: past that, a fixed seeded sample of each array's elements)" % DUMP_LIMIT_BYTES)
@@ -124,6 +134,9 @@ def main():
         ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.dump_outputs is not None and args.workload == "potrf":
         ap.error("--dump-outputs: the potrf workload has no step loop")
+    if args.full and args.only_value:
+        ap.error("--full and --only-value contradict each other")
+    args.only_value = not args.full                   # (what benchlib reads: the plain run measures the headline and nothing else)
 
     # `python bench.py --gpus N` (no launcher): start the N ranks ourselves.  This process has not touched the GPU (torch is not
     # even imported yet) and never will: the ranks are a fresh `torch.distributed.run` child, whose rank 0 prints the line.
@@ -158,10 +171,11 @@ def main():
         os.environ.setdefault("RANK", "0")
         os.environ.setdefault("WORLD_SIZE", "1")
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        if backend == "nccl":
-            td.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
-        else:
-            td.init_process_group(backend, rank=rank, world_size=world)
+        # no device_id: RCCL then creates its communicator -- and its streams -- at the first collective, after the model's
+        # context has created its four.  The runtime hands hardware queues (GPU_MAX_HW_QUEUES, 4 by default) to streams in
+        # the order they are created; created first, RCCL's streams leave the context's streams sharing queues, and the one-rank
+        # step measured 1.63 ms for 0.86 created lazily.
+        td.init_process_group(backend, rank=rank, world_size=world)
 
     if args.sub_result is not None:                   # one sub-result of the default line, as a command of its own
         legs = []
@@ -173,7 +187,7 @@ def main():
         return
     if args.workload == "potrf":                      # the dense Cholesky path on its own (the command profiled as r04_*_potrf)
         if rank == 0:
-            emit(potrf_bench())
+            emit(dict(potrf_bench(full=args.full), full=args.full))
         return
     w = workload(args.workload)
     # Every GPU measurement of this process runs BEFORE any CPU leg (oracle parity checks, the CPU baseline's BLAS-thread sweep):
@@ -186,11 +200,11 @@ def main():
         out = run_fit_bench(args, w, rank, world, local_rank, backend, cpu_legs=cpu_legs, outputs=outputs)
     else:
         out = run_step_bench(args, w, rank, world, local_rank, backend, cpu_legs=cpu_legs, outputs=outputs)
-    # the driver runs `bench.py --gpus 1` only: carry compact cfg2 / cfg5 / potrf / npx69 / aud24 results with that run (N=1, a few
-    # seconds each); their headline scalars go into `config` of the line, the full dicts into the detail file
+    # --full at N=1 carries compact cfg2 / cfg5 / potrf / npx69 / aud24 results with the cfg3 run (a few seconds each); their
+    # headline scalars go into `config` of the line, the full dicts into the detail file
     sub = None
     if (rank == 0 and out is not None and world == 1 and args.workload == "cfg3" and args.trials_per_gpu is None
-            and not args.only_value and not args.no_sub_results):
+            and args.full and not args.no_sub_results):
         sub = sub_results(args, local_rank, backend, cpu_legs)
     for leg in cpu_legs:
         leg()
@@ -198,6 +212,7 @@ def main():
         out["sub_results"] = sub
         out["config"].update(sub_headlines(sub))
     if rank == 0 and out is not None:
+        out["full"] = args.full
         out["host_affinity"] = ({"bound_to_numa_node": host_numa["node"], "cpus": host_numa["cpus"], "device_pci": host_numa["pci"]}
                                 if host_numa else {"bound_to_numa_node": None, "cpus": len(os.sched_getaffinity(0))})
         if outputs is not None:
@@ -260,6 +275,7 @@ def sub_result_one(args, key, local_rank, backend, cpu_legs):
     def step(name, steps, warmup, setup):
         a = copy.copy(args)
         a.workload, a.steps, a.warmup, a.setup_steps, a.no_cpu_baseline, a.trials_per_gpu = name, steps, warmup, setup, True, None
+        a.only_value = False
         r = run_step_bench(a, workload(name), 0, 1, local_rank, backend, compact=True, cpu_legs=cpu_legs)
         r["fenced_calls_ms"] = [r["fenced_calls"]["loglik_ms"], r["fenced_calls"]["predict_resident_ms"]]
         r["loglik_evals_per_sec"] = r["fenced_calls"]["loglik_evals_per_sec_per_gpu"]
@@ -272,6 +288,7 @@ def sub_result_one(args, key, local_rank, backend, cpu_legs):
     def fit(name):
         a = copy.copy(args)
         a.workload, a.steps, a.warmup, a.setup_steps, a.fit_batch, a.fit_groups = name, 40, 3, 30, None, 1
+        a.only_value = False
         r = run_fit_bench(a, workload(name), 0, 1, local_rank, backend, compact=True, cpu_legs=cpu_legs)
         roof = r.pop("roofline", None) or {}
         r["roofline_frac_step_executed"], r["hbm_traffic_bytes_per_step"] = roof.get("frac"), roof.get("traffic")

@@ -13,11 +13,12 @@ from .profiles import pmc_step_traffic
 from .workloads import FP64_MFMA_SPEC_TFLOPS, SETTLE_S, build_model, oracle_setup, synth_data
 
 
-def potrf_bench(n=12000, reps=3):
+def potrf_bench(n=12000, reps=3, full=True):
     """The dense Cholesky path (north_star: "(Ks (x) Kt + sig2 I) Cholesky factor, log-det and triangular solves") at the one size of
     BASELINE's configurations where the dense matrix fits one GPU -- cfg2's N = 24 x 500 = 12 000 (1.15 GB): the blocked factorisation
     on a device-resident SPD matrix (gpcsd_potrf_bench: HIP events on the library's stream around the factorisation alone), n^3 / 3
-    flops against the fp64 MFMA peak, with the event-scope split of one profiled factorisation."""
+    flops against the fp64 MFMA peak; with `full`, the event-scope split of one profiled factorisation and the diagonal-block phases
+    beside it."""
     from gpcsd_amd import _hip
     ctx = _hip.default_context()
     _quiesce_host()
@@ -28,6 +29,12 @@ def potrf_bench(n=12000, reps=3):
     runs = sorted(ctx.potrf_bench(n, reps=1) for _ in range(max(3, reps)))
     ms, tf = runs[len(runs) // 2]
     gate_timeouts = ctx.potrf_gate_timeouts() - g0         # (gates that gave up waiting: they steer the order of execution only)
+    out = {"metric": "gpcsd_dense_cholesky_factorisations_per_sec", "value": 1e3 / ms, "unit": "factorisations/s", "n": n, "ms": ms,
+           "dtype": "f64", "flops": n ** 3 / 3.0, "tflops": tf, "frac_of_fp64_mfma_peak": tf / FP64_MFMA_SPEC_TFLOPS,
+           "gate_timeouts": gate_timeouts,
+           "config": {"workload": "blocked Cholesky of a %d x %d SPD matrix resident in HBM (N of BASELINE cfg2: 24 x 500)" % (n, n)}}
+    if not full:
+        return out
     ctx.prof_reset()
     ctx.prof_enable(1)
     ctx.potrf_bench(n, reps=1)
@@ -37,13 +44,10 @@ def potrf_bench(n=12000, reps=3):
     split = {k: {"ms": v["ms"] / 2.0, "launches": v["count"] // 2,
                  "tflops": ((v["flops"] / 2.0) / (v["ms"] / 2.0 * 1e-3) / 1e12) if (v["ms"] and v["flops"]) else None} for k, v in prof.items()}
     tu = split.get("potrf_syrk", {})
-    out = {"metric": "gpcsd_dense_cholesky_factorisations_per_sec", "value": 1e3 / ms, "unit": "factorisations/s", "n": n, "ms": ms,
-           "dtype": "f64", "flops": n ** 3 / 3.0, "tflops": tf, "frac_of_fp64_mfma_peak": tf / FP64_MFMA_SPEC_TFLOPS,
-           "trailing_update": {"kernel": "gemm_f64_kernel<EPI_SUB, lower> [potrf_syrk]: rank-256 update A22 -= L21 L21^T, tiles on or "
-                                         "below the diagonal", "ms": tu.get("ms"), "launches": tu.get("launches"),
-                               "tflops": tu.get("tflops"), "frac": (tu.get("tflops") or 0.0) / FP64_MFMA_SPEC_TFLOPS},
-           "scopes": split, "diag128_phases_us": ctx.potrf_diag_probe(), "gate_timeouts": gate_timeouts,
-           "config": {"workload": "blocked Cholesky of a %d x %d SPD matrix resident in HBM (N of BASELINE cfg2: 24 x 500)" % (n, n)}}
+    out.update(trailing_update={"kernel": "gemm_f64_kernel<EPI_SUB, lower> [potrf_syrk]: rank-256 update A22 -= L21 L21^T, tiles on "
+                                          "or below the diagonal", "ms": tu.get("ms"), "launches": tu.get("launches"),
+                                "tflops": tu.get("tflops"), "frac": (tu.get("tflops") or 0.0) / FP64_MFMA_SPEC_TFLOPS},
+               scopes=split, diag128_phases_us=ctx.potrf_diag_probe())
     out["headline"] = {"ms": ms, "frac": out["frac_of_fp64_mfma_peak"], "trailing_update_frac": out["trailing_update"]["frac"]}
     return out
 
@@ -152,14 +156,25 @@ def run_fit_bench(args, w, rank, world, local_rank, backend, compact=False, cpu_
     if outputs is not None:                # what the timed loop's last step returned, groups one after the other
         for i, name in enumerate(("sumlog", "quad", "grad")):
             outputs[name] = np.concatenate([r[i] for r in last])
-    if args.only_value:                    # the command the rocprofv3 passes under profiles/ are taken over: nothing after the loop
+
+    def max_over_ranks(*vals):                  # a sharded job takes as long as its slowest rank
+        if sharding is None:
+            return vals
+        import torch.distributed as td
+        tt = torch.tensor(vals, dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
+        td.all_reduce(tt, op=td.ReduceOp.MAX)
+        return tuple(float(v) for v in tt.cpu())
+    dtype = "f64" if m.gram_precision == 64 else "f32 Gram build + f64"
+    if args.only_value:                      # the plain run (and the command the rocprofv3 passes under profiles/ are taken over)
+        elapsed, = max_over_ranks(elapsed)
         if rank != 0:
             return None
         return {"metric": "gpcsd_fit_loglik_grad_evals_per_sec", "value": G * B * world * args.steps / elapsed, "unit": "evals/s",
-                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-                "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "setup_steps": max(3, min(args.setup_steps, 20)),
+                "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+                "dtype": dtype, "data": "synthetic",
                 "config": {"workload": w["label"], "n_elec": w["nx"], "n_t": w["nt"], "trials_per_gpu": w["trials_per_gpu"],
-                           "lockstep_batch": B}, "only_value": "setup + warm-up + timed loop only (the command profiled under profiles/)"}
+                           "restarts_total": total_restarts, "restarts_per_gpu": len(mine), "lockstep_batch": B}}
     # one group alone, for reference
     fence()
     t0g = time.perf_counter()
@@ -204,11 +219,7 @@ def run_fit_bench(args, w, rank, world, local_rank, backend, compact=False, cpu_
             ctx.loglik_parts(hps[0])
         ll_fenced_ms = 1e3 * (time.perf_counter() - tl) / 20
         ctx.decomposition_cache(True)
-    if sharding is not None:
-        import torch.distributed as td
-        tt = torch.tensor([elapsed, seq_s], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
-        td.all_reduce(tt, op=td.ReduceOp.MAX)
-        elapsed, seq_s = (float(v) for v in tt.cpu())
+    elapsed, seq_s = max_over_ranks(elapsed, seq_s)
     # profiled pass of the batched step
     ctx.prof_reset()
     ctx.prof_enable(True)
@@ -335,7 +346,7 @@ def run_fit_bench(args, w, rank, world, local_rank, backend, compact=False, cpu_
         "value": n_eval / elapsed, "unit": "evals/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "setup_steps": max(3, min(args.setup_steps, 20)),
         "ms_per_step": 1e3 * step_s, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": "f64" if m.gram_precision == 64 else "f32 Gram build + f64", "data": "synthetic",
+        "dtype": dtype, "data": "synthetic",
         "config": {"workload": w["label"], "n_elec": w["nx"], "n_t": w["nt"], "trials_per_gpu": w["trials_per_gpu"],
                    "restarts_total": total_restarts, "restarts_per_gpu": len(mine), "lockstep_batch": B, "lockstep_groups": G,
                    "parallelism": "restart-sharded x%d, %d lock-step groups of %d restarts per GPU" % (world, G, B)},

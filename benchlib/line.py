@@ -35,7 +35,7 @@ DETAIL_FILE = "bench_detail.json"
 _TOP_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "setup_steps", "ms_per_step", "higher_is_better", "scaling",
              "vs_baseline", "dtype", "data", "loglik", "parity_rel_err_loglik_vs_oracle", "parity_rel_err_predict_vs_oracle",
              "n", "ms", "tflops", "frac_of_fp64_mfma_peak", "evals_per_sec_one_at_a_time_per_gpu", "batched_over_sequential",
-             "only_value")
+             "full")
 _NESTED_KEYS = {
     "config": ("workload", "n_elec", "n_t", "trials_per_gpu", "total_trials", "parallelism", "restarts_total", "restarts_per_gpu",
                "lockstep_batch", "class_api_predict_trials_per_sec", "class_api_predict_host_gb_per_sec",

@@ -148,16 +148,18 @@ def run_step_bench(args, w, rank, world, local_rank, backend, compact=False, cpu
     dist_info = None
     if sharding is not None:
         import torch.distributed as td
-        # the same steps on every rank WITHOUT the collective (each rank alone with its card, as an N = 1 run): what the
-        # sharded job's rate is quoted against when no N = 1 figure is handed in (--n1-value)
-        for _ in range(min(args.warmup, 3)):
-            solo_step()
-        ctx.synchronize()
-        tsolo = time.perf_counter()
-        for _ in range(args.steps):
-            solo_step()
-        ctx.synchronize()
-        solo = time.perf_counter() - tsolo
+        solo = 0.0
+        if not args.only_value:
+            # the same steps on every rank WITHOUT the collective (each rank alone with its card, as an N = 1 run): what the
+            # sharded job's rate is quoted against when no N = 1 figure is handed in (--n1-value)
+            for _ in range(min(args.warmup, 3)):
+                solo_step()
+            ctx.synchronize()
+            tsolo = time.perf_counter()
+            for _ in range(args.steps):
+                solo_step()
+            ctx.synchronize()
+            solo = time.perf_counter() - tsolo
         dev = "cuda" if backend == "nccl" else "cpu"
         per_rank = torch.zeros(2 * world, dtype=torch.float64, device=dev)
         per_rank[rank], per_rank[world + rank] = elapsed, solo
@@ -166,18 +168,22 @@ def run_step_bench(args, w, rank, world, local_rank, backend, compact=False, cpu
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         td.all_reduce(tt, op=td.ReduceOp.MAX)
         elapsed = float(tt.cpu()[0])
-        unsharded_rate = float(np.sum(R_local * args.steps / per_rank[world:]))
         value_now = R_total * args.steps / elapsed
         dist_info = {
             "collective_backend": td.get_backend(), "rccl_ranks": td.get_world_size() if td.get_backend() == "nccl" else 0,
             "ranks": td.get_world_size(),
             "per_rank_ms_per_step": [1e3 * float(v) / args.steps for v in per_rank[:world]],
-            "per_rank_ms_per_step_without_collectives": [1e3 * float(v) / args.steps for v in per_rank[world:]],
-            "efficiency_vs_ranks_without_collectives": value_now / unsharded_rate,
-            "scaling_efficiency": (value_now / (world * args.n1_value)) if args.n1_value else value_now / unsharded_rate,
-            "scaling_efficiency_against": ("--n1-value %.6g trials/s" % args.n1_value) if args.n1_value else
-                                          "sum of the ranks' own rates over the same steps without the all-reduce (same processes)",
         }
+        if not args.only_value:
+            unsharded_rate = float(np.sum(R_local * args.steps / per_rank[world:]))
+            dist_info["per_rank_ms_per_step_without_collectives"] = [1e3 * float(v) / args.steps for v in per_rank[world:]]
+            dist_info["efficiency_vs_ranks_without_collectives"] = value_now / unsharded_rate
+            dist_info["scaling_efficiency"] = value_now / unsharded_rate
+            dist_info["scaling_efficiency_against"] = ("sum of the ranks' own rates over the same steps without the all-reduce "
+                                                       "(same processes)")
+        if args.n1_value:
+            dist_info["scaling_efficiency"] = value_now / (world * args.n1_value)
+            dist_info["scaling_efficiency_against"] = "--n1-value %.6g trials/s" % args.n1_value
     ms_per_step = 1e3 * elapsed / args.steps
     pf_queued, pf_taken = ctx.prefetch_stats()
     # the prediction the TIMED loop's last step left in HBM, in the mode `value` is timed in (announced, one spatial decomposition
@@ -185,7 +191,7 @@ def run_step_bench(args, w, rank, world, local_rank, backend, compact=False, cpu
     timed_pred = None
     if not args.only_value and world == 1:
         timed_pred = {"csd": ctx.fetch("pred_out_csd", (z.shape[0], w["nt"], R_local)).copy()}
-    if args.only_value:
+    if args.only_value:                      # the plain run (and the command the rocprofv3 passes under profiles/ are taken over)
         if rank != 0:
             return None
         return {"metric": "gpcsd_loglik_plus_predict_trials_per_sec", "value": R_total * args.steps / elapsed, "unit": "trials/s",
@@ -195,7 +201,7 @@ def run_step_bench(args, w, rank, world, local_rank, backend, compact=False, cpu
                 "config": {"workload": w["label"], "n_elec": w["nx"], "n_t": w["nt"], "trials_per_gpu": R_local,
                            "total_trials": R_total, "parallelism": "trial-sharded x%d" % n_gpus,
                            "next_step_announced": bool(announce["on"]), "pair_shares_spatial_side": bool(share_s)},
-                "only_value": "setup + warm-up + timed loop only (the command profiled under profiles/)", "distributed": dist_info}
+                "distributed": dist_info}
 
     # ---- the two halves on their own (rank-local, every call fenced: nothing of one call overlaps the next) ----
     # In the step loop above predict_resident returns with its GEMM tail in flight (its results stay on the device) and

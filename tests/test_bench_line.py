@@ -117,3 +117,33 @@ def test_sub_results_run_as_child_commands_and_a_failed_one_leaves_nulls(monkeyp
     h = bench.sub_headlines(sub)
     assert h["cfg2_ms_per_step"] == 0.5 and h["cfg5_evals_per_sec"] is None and h["potrf_frac"] == 0.4
     assert set(bench.SUB_RESULT_KEYS) == {"cfg2", "cfg3fit", "cfg5", "npx69", "aud24", "potrf"}
+
+
+def test_full_and_only_value_are_refused_together(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--only-value"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
+
+
+@pytest.mark.gpu
+def test_a_plain_run_prints_the_headline_alone_and_full_adds_the_rest():
+    """A plain run sets up, warms up, times its steps and prints the line: nothing is measured beside the headline.  --full
+    measures the rest after the same timed loop (fenced halves, roofline passes, ...) and says so in the line."""
+    import subprocess
+    common = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg2", "--trials-per-gpu", "6", "--steps", "3",
+              "--warmup", "1", "--setup-steps", "3"]
+    recs = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        r = subprocess.run(common + extra, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        recs[mode] = json.loads(r.stdout.strip().splitlines()[-1])
+    plain, full = recs["plain"], recs["full"]
+    for rec in (plain, full):
+        assert rec["metric"] == "gpcsd_loglik_plus_predict_trials_per_sec" and rec["unit"] == "trials/s" and rec["dtype"] == "f64"
+        assert rec["higher_is_better"] is True and rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+        assert rec["value"] == pytest.approx(6 * 3 / (3 * rec["ms_per_step"] * 1e-3))
+    assert plain["full"] is False and full["full"] is True
+    assert "roofline" not in plain and "fenced_loglik_ms" not in plain["config"]
+    assert full["roofline"]["frac"] > 0 and full["config"]["fenced_loglik_ms"] > 0
+    assert plain["loglik"] == full["loglik"]                 # the same seeded trials and hyper-parameters

@@ -938,7 +938,7 @@ def test_bench_step_two_ranks_gloo_on_one_gpu():
     common = ["--steps", "2", "--warmup", "1", "--setup-steps", "3", "--trials-per-gpu", "4", "--no-cpu-baseline"]
     # the driver's own command form: no launcher in front -- bench.py starts its two ranks itself (a fresh torch.distributed.run
     # child of a parent that never touched the GPU) and relays rank 0's line
-    two = _run([sys.executable, "bench.py", "--gpus", "2"] + common, env)
+    two = _run([sys.executable, "bench.py", "--gpus", "2"] + common + ["--full"], env)
     assert two["n_gpus"] == 2 and two["config"]["total_trials"] == 8 and two["value"] > 0 and two["setup_steps"] == 3 + 400    # (+ the settle steps of a sharded loop: bench.SETTLE_S)
     d = two["distributed"]
     assert d["ranks"] == 2 and d["collective_backend"] == "gloo" and d["rccl_ranks"] == 0 and len(d["per_rank_ms_per_step"]) == 2
@@ -965,7 +965,7 @@ def test_bench_cfg5_two_ranks_restart_sharding_over_the_hip_objective():
     lock-step groups run the real HIP objective, and the combined fit equals the single-process fit of all 32 restarts."""
     env = dict(os.environ, GPCSD_BENCH_BACKEND="gloo", GPCSD_DEVICE="0", MASTER_ADDR="127.0.0.1")
     port = 29900 + os.getpid() % 400
-    common = ["--workload", "cfg5", "--steps", "3", "--warmup", "1", "--fit-maxiter", "4"]
+    common = ["--workload", "cfg5", "--steps", "3", "--warmup", "1", "--fit-maxiter", "4", "--full"]
     two = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                 "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2"] + common, env)
     # torch.distributed.run pins OMP_NUM_THREADS=1 in its workers; the synthetic data come out of NumPy matmuls whose rounding
