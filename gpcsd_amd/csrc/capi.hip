@@ -4,6 +4,7 @@
 #include <functional>
 #include <cmath>
 #include <mutex>
+#include <optional>
 
 #include "kernels.hpp"
 #include "jacobi.hpp"
@@ -391,7 +392,12 @@ void eig_pair_D(gpcsd_ctx *c, double *Ks, int nx, double *Kt, int nt, const doub
     {
         // all problems share every launch of the per-column tridiagonalisation (batched), so one stream suffices
         ProfScope ps(c, "eigh_pair", 9.0 * ((double)nx * nx * nx + (double)nt * nt * nt), c->stream);
-        eigh_pair_device(c, Ks, nx, es, Qs, sym_s, Kt, nt, et, Qt, sym_t, d_status, c->stream, need_merged);
+        EighCall r;
+        r.side[0] = {Ks, nx, es, Qs, sym_s};
+        r.side[1] = {Kt, nt, et, Qt, sym_t};
+        r.status = d_status;
+        r.need_merged = need_merged;
+        eigh_pair_device(c, r, c->stream);
     }
     k_build_D(c, es, nx, et, nt, d_sig, nsig, D, Dinv, d_sumlog, c->stream);
 }
@@ -411,19 +417,18 @@ struct EigState {
     bool tri = false, wait_q = false;
     int tri_rep = 0, tri_count = 1;
     // tri: stage 1 ran with progress words and NO stage 3 was queued -- loglik_tri_pre queues stage 5 instead (queue_q_pipeline:
-    // T factors and Q on stream4, X = Y~ Q block of columns by block on the main stream), with the arguments of the stage-1 call
+    // T factors and Q on stream4, X = Y~ Q block of columns by block on the main stream): the chain's stage-5 request (TChain),
+    // the replica whose Q forms X, and what gpcsd_ctx::q_gen becomes once Q is queued
     bool pipe_pending = false;
     struct {
-        double *Kt = nullptr, *et = nullptr, *Qt = nullptr;
-        const SymDev *sym_t = nullptr;
-        int *status = nullptr;
-        int nt = 0, nT = 1, stride = 0, rep = 0, q_gen = -1;
-        bool need_merged = false;
+        EighCall req;
+        int rep = 0;
+        long q_gen = -1;
     } pa;
 };
 
 // Stage 5 instead of stage 3 (gpcsd_ctx::q_pipe): both halves whole in the register tail, the temporal product first in the
-// log-likelihood's tail (GPCSD_LL_ORDER=0), and the caller has promised to form X through loglik_tri_pre (q_pipe_want).
+// log-likelihood's tail (GPCSD_LL_ORDER=0), and the caller has promised to form X through loglik_tri_pre (x_via_tri_pre).
 static int ll_order() {                    // GPCSD_LL_ORDER: order of the log-likelihood's two products (capi_fused.inl)
     static const int o = getenv("GPCSD_LL_ORDER") ? atoi(getenv("GPCSD_LL_ORDER")) : 0;
     return o;
@@ -436,20 +441,12 @@ static bool q_stage5_applies(const gpcsd_ctx *c, const SymDev *sym_t) {
     return sym_t && std::max(sym_t->ns, sym_t->na) <= eigh_regtail_rows() &&
            k_tridiag_solve_pass(std::max(sym_t->ns, sym_t->na), c->ntrials) > 0;
 }
-// ... and pipelined (gpcsd_ctx::q_pipe) when the caller has promised to form X through loglik_tri_pre (q_pipe_want) with the
+// ... and pipelined (gpcsd_ctx::q_pipe) when the caller has promised to form X through loglik_tri_pre (x_via_tri_pre) with the
 // temporal product first in the log-likelihood's tail (GPCSD_LL_ORDER=0)
-static bool q_pipe_applies(const gpcsd_ctx *c, const SymDev *sym_t) {
-    return c->q_pipe && c->q_pipe_want && ll_order() == 0 && q_stage5_applies(c, sym_t);
+static bool q_pipe_applies(const gpcsd_ctx *c, const SymDev *sym_t, bool x_via_tri_pre) {
+    return c->q_pipe && x_via_tri_pre && ll_order() == 0 && q_stage5_applies(c, sym_t);
 }
-// Stage 5 unpipelined: behind the end of stage 1, Q only (the caller forms X itself)
-static void queue_stage5_plain(gpcsd_ctx *c, double *Kt, int nt, double *et, double *Qt, const SymDev *sym_t, int *status,
-                               bool need_merged, int nT, int stride) {
-    hipStream_t sq = c->stream4;
-    GP_HIP(hipStreamWaitEvent(sq, c->ev_t1, 0));
-    GP_HIP(hipStreamWaitEvent(sq, c->ev_pc, 0));      // (stream5's readers of the Q about to be rewritten)
-    c->q_pipe_x = gpcsd_ctx::QPipeX();
-    eigh_pair_device(c, nullptr, 0, nullptr, nullptr, nullptr, Kt, nt, et, Qt, sym_t, status, sq, need_merged, nT, stride, -1, 2, /*stage=*/5);
-}
+
 // Queue stage 5 (EigState::pipe_pending): on stream4, behind ev_t0, T factor and forward apply panel by panel under the running
 // stage 1; on the main stream, behind an event per panel, X[:, panel's columns] = src Q[:, panel's columns] -> xname (eigh_dc.hip).
 // The main stream is in order behind every earlier reader of X and behind whatever built src.
@@ -457,21 +454,13 @@ static void queue_q_pipeline(gpcsd_ctx *c, EigState &e, const double *src, const
     hipStream_t sq = c->stream4;
     GP_HIP(hipStreamWaitEvent(sq, c->ev_t0, 0));
     GP_HIP(hipStreamWaitEvent(sq, c->ev_pc, 0));      // the side stream's last readers of Q (the previous predictions' Pcat products)
-    gpcsd_ctx::QPipeX x;
-    x.in = src;
-    x.out = c->buf<double>(xname, (size_t)c->nx * c->ntrials * c->nt);
-    x.M = c->nx * c->ntrials; x.ld = e.pa.nt;
-    x.c0[0] = 0; x.c0[1] = e.pa.sym_t->ns;
-    x.rep = e.pa.rep;
-    c->q_pipe_x = x;
-    try {
-        eigh_pair_device(c, nullptr, 0, nullptr, nullptr, nullptr, e.pa.Kt, e.pa.nt, e.pa.et, e.pa.Qt, e.pa.sym_t, e.pa.status, sq,
-                         e.pa.need_merged, e.pa.nT, e.pa.stride, -1, 2, /*stage=*/5);
-    } catch (...) {
-        c->q_pipe_x = gpcsd_ctx::QPipeX();
-        throw;
-    }
-    c->q_pipe_x = gpcsd_ctx::QPipeX();
+    EighCall r = e.pa.req;
+    r.x.in = src;
+    r.x.out = c->buf<double>(xname, (size_t)c->nx * c->ntrials * c->nt);
+    r.x.M = c->nx * c->ntrials; r.x.ld = r.side[1].n;
+    r.x.c0[0] = 0; r.x.c0[1] = r.side[1].sym->ns;
+    r.x.rep = e.pa.rep;
+    eigh_pair_device(c, r, sq);
     GP_HIP(hipEventRecord(c->ev_q[c->tgen], sq));
     c->tl("Q end", sq);
     c->q_queued[c->tgen] = true;
@@ -532,6 +521,120 @@ static void clear_late_status(gpcsd_ctx *c, int *status, hipStream_t s2, bool st
     GP_HIP(hipMemsetAsync(status + gpcsd_ctx::STATUS_LATE, 0, (gpcsd_ctx::STATUS_N - gpcsd_ctx::STATUS_LATE) * sizeof(int), s2));
 }
 
+// The plan of one temporal eigen-chain, the critical path of every fused call: tridiagonalisation -> T factors / Q -> divide &
+// conquer -> back-transformation, in stages 1, 2, 4 on stream2 with 3 (or 5) beside them on stream4 -- or the whole solve where
+// staging does not apply.  tchain_begin / tchain_finish are the ONE place that queues it; a paired call queues its spatial chain
+// between the two.
+struct TChain {
+    // nT replicas (the sets hp[0..nT) on the time grid t) of Kt (nt, nt: destroyed); merged spectrum / eigenvectors when need_merged
+    double *Kt = nullptr, *et = nullptr, *Qt = nullptr;
+    const SymDev *sym_t = nullptr;
+    const gpcsd_hparams *const *hp = nullptr;
+    const double *t = nullptr;
+    int nt = 0, nT = 1;
+    bool need_merged = false;
+    // the call's status words: replica r reports into status[1 + r * stride], its stages 2 and 4 into status[STATUS_LATE + 1 + r * stride]
+    int *status = nullptr, stride = 0;
+    bool tfill = false;            // the input goes straight into the class arenas (temporal_fill), else through the caller's builder
+    bool staged = false;
+    bool tri = false;              // staged, and no consumer takes the eigenvector form: stages 2 and 4 are not queued
+    bool x_via_tri_pre = false;    // the caller forms X = Y~ Q through loglik_tri_pre (the pipeline may apply)
+    bool st5 = false, pipe = false;      // (tchain_begin) stage 5's kernels instead of stage 3's; ... queued later, under the running stage 1
+    bool single = false;           // one set, as the decomposition cache looks for it: gpcsd_ctx::q_gen = eig_gen[1] (replicas: -1)
+    const char *scope2 = nullptr;  // profile scope of tchain_finish (nullptr: tchain_begin's stays open across both)
+    std::optional<ProfScope> ps;
+
+    TChain(gpcsd_ctx *c, const SymDev *sy, int n, bool host_kt) : sym_t(sy), nt(n) {
+        tfill = temporal_fill_applies(c, sym_t, nt, host_kt);
+        staged = tfill && ll_tridiag_enabled(c) && eigh_stageable(sym_t, nt);
+    }
+    EighCall request(int stage) const {
+        EighCall r;
+        r.side[1] = {Kt, nt, et, Qt, sym_t, nT, /*prefolded=*/tfill};
+        r.status = status + 1 + ((stage == 2 || stage == 4) ? gpcsd_ctx::STATUS_LATE : 0);
+        r.status_stride = stride;
+        r.need_merged = need_merged;
+        r.stage = stage;
+        r.progress = stage == 1 && st5;        // the tail publishes its progress: stage 5 follows
+        return r;
+    }
+    long q_gen(const gpcsd_ctx *c) const { return single ? c->eig_gen[1] : -1; }
+};
+static void tchain_end(gpcsd_ctx *c, TChain &p) {
+    p.ps.reset();
+    GP_HIP(hipEventRecord(c->ev_join, c->stream2));
+    c->tl("T chain end (s2)", c->stream2);
+}
+// The other generation of the class arenas, the guard against the predecessor's readers, the input, the late status words, then
+// stage 1 (or the whole solve).  build_kt(stream): the caller's builder of Kt where temporal_fill does not apply.
+template <class BuildKt>
+static void tchain_begin(gpcsd_ctx *c, TChain &p, BuildKt &&build_kt) {
+    hipStream_t s2 = c->stream2;
+    c->tl("T chain start (s2)", s2);
+    c->tgen ^= 1;                        // the other generation of the temporal class arenas (gpcsd_ctx::tgen)
+    staged_chain_guard(c, s2);
+    if (p.tfill) temporal_fill(c, p.hp, p.nT, p.t, p.nt, *p.sym_t, p.status + 1, p.stride, s2);
+    else build_kt(s2);
+    clear_late_status(c, p.status, s2, p.staged && !p.tri);       // (words 4 and up; the fill reports into 1 / 3)
+    // stage 5 instead of stage 3 only when nobody takes the eigenvector form: a stage 4 behind stage 5 would read T factors summed in
+    // another order than stage 3's, and a pair would differ from its fenced calls in the last bits
+    p.st5 = p.staged && p.tri && q_stage5_applies(c, p.sym_t);                  // T, Q by stage 5's kernels
+    p.pipe = p.st5 && q_pipe_applies(c, p.sym_t, p.x_via_tri_pre);              // ... under the running stage 1
+    p.ps.emplace(c, "eigh_temporal", 9.0 * (double)p.nt * p.nt * p.nt * p.nT, s2);
+    if (!p.staged) {
+        eigh_pair_device(c, p.request(0), s2);
+        tchain_end(c, p);
+        return;
+    }
+    // staged whenever it applies: the T factors are then a launch of their own instead of riding in the leaf launch (same bits
+    // either way).  A log-likelihood in the tridiagonal form starts its tail behind stages 1 and 3 and never waits for 2 and 4.
+    if (p.pipe) GP_HIP(hipEventRecord(c->ev_t0, s2));
+    eigh_pair_device(c, p.request(1), s2);
+    GP_HIP(hipEventRecord(c->ev_t1, s2));
+    c->tl("T stage 1 end (s2)", s2);
+    if (p.scope2) p.ps.reset();
+}
+// Staged chains only: stage 2 (divide & conquer) on the chain's stream; beside it, on stream4, stage 3 (T factors, Q) or an
+// unpipelined stage 5 (Q only: the caller forms X itself); stage 4 (back-transformation) behind both.  With tridiagonal-form
+// consumers only: stage 3 / 5 alone -- and a pipelined stage 5 is queued by the log-likelihood's loglik_tri_pre
+// (EigState::pipe_pending).  (Stage 3 on the main stream, in front of X: 1.14 against 1.10 ms -- that stream is rarely idle then.)
+static void tchain_finish(gpcsd_ctx *c, TChain &p) {
+    if (!p.staged) return;
+    hipStream_t s2 = c->stream2, sq = c->stream4;
+    if (p.scope2) p.ps.emplace(c, p.scope2, 0.0, s2);
+    if (!p.tri) eigh_pair_device(c, p.request(2), s2);
+    if (p.pipe) {
+        c->q_queued[c->tgen] = false;
+        c->q_gen = -1;                   // (until stage 5 is queued)
+    } else {
+        GP_HIP(hipStreamWaitEvent(sq, c->ev_t1, 0));
+        GP_HIP(hipStreamWaitEvent(sq, c->ev_pc, 0));          // (stream5's readers of the Q about to be rewritten)
+        eigh_pair_device(c, p.request(p.st5 ? 5 : 3), sq);
+        GP_HIP(hipEventRecord(c->ev_q[c->tgen], sq));
+        c->tl("Q end", sq);
+        c->q_queued[c->tgen] = true;
+        c->q_gen = p.q_gen(c);
+    }
+    if (!p.tri) {
+        GP_HIP(hipStreamWaitEvent(s2, c->ev_q[c->tgen], 0));
+        eigh_pair_device(c, p.request(4), s2);
+    }
+    tchain_end(c, p);
+}
+// What a tridiagonal-form consumer of replica `rep` of the chain's classes needs to know (EigState::tri ...); forms_x: it is the
+// one whose loglik_tri_pre forms X and queues a pipelined stage 5.
+static void tchain_consumer(const gpcsd_ctx *c, const TChain &p, EigState &e, int rep, bool forms_x) {
+    e.tri = e.wait_q = true;
+    e.tri_rep = rep;
+    e.tri_count = p.nT;
+    if (p.pipe && forms_x) {
+        e.pipe_pending = true;
+        e.pa.req = p.request(5);
+        e.pa.rep = rep;
+        e.pa.q_gen = p.q_gen(c);
+    }
+}
+
 // Main stream waits for the spatial chain of this call (no-op when it was reused from the cache or already joined).
 static void join_spatial(gpcsd_ctx *c, EigState &e) {
     if (e.wait_spatial) {
@@ -574,9 +677,10 @@ static bool two_stream_front() {            // GPCSD_TWO_STREAM=0: single batche
 // stale spectra -- such callers rebuild it in fold order (join_temporal with a FoldMode).
 // join_s = false: the caller calls join_spatial() itself.  Fold views (fold_mode) must be taken AFTER this returns.
 // want_tri: the caller's tail works from the temporal tridiagonalisation + Q alone (EigState::tri tells it whether it may).
+// x_via_tri_pre: ... and forms X = Y~ Q through loglik_tri_pre, where a pipelined stage 5 is queued (TChain).
 // merged_s: the spatial side's merged spectrum and eigenvectors are wanted although the temporal side's are not (-1: as need_merged).
 EigState front_half(gpcsd_ctx *c, const gpcsd_hparams *hp, double jitter, bool need_merged = true, bool join_s = true,
-                    bool want_tri = false, int merged_s = -1) {
+                    bool want_tri = false, int merged_s = -1, bool x_via_tri_pre = false) {
     const bool need_merged_s = merged_s < 0 ? need_merged : merged_s != 0;
     const Geo g = resident_geo(c);
     GP_REQUIRE(c->d_lfp != nullptr, -4, "lfp not set (call gpcsd_set_lfp)");
@@ -648,9 +752,8 @@ EigState front_half(gpcsd_ctx *c, const gpcsd_hparams *hp, double jitter, bool n
     }
     // can this call's consumer take the tridiagonal form?  (decided before the cache is asked: a cached side that stopped at the
     // tridiagonalisation only serves such consumers)
-    const bool tfill0 = temporal_fill_applies(c, sym_t, nt, host_kt);
-    const bool staged0 = tfill0 && ll_tridiag_enabled(c) && eigh_stageable(sym_t, nt);
-    const bool tri_consumer = staged0 && want_tri && !need_merged && hp->n_sig2n == 1;
+    TChain tc(c, sym_t, nt, host_kt);
+    const bool tri_consumer = tc.staged && want_tri && !need_merged && hp->n_sig2n == 1;
     bool run_t = !decomp_cached(c, 1, &kt_key, sizeof(kt_key));
     if (!run_t && !tri_consumer && !c->decomp_t_full) {      // cached, but only as far as a tridiagonal-form consumer needs
         run_t = true;
@@ -675,73 +778,14 @@ EigState front_half(gpcsd_ctx *c, const gpcsd_hparams *hp, double jitter, bool n
     outputs();
     c->tl("call start (main)", s);
     if (run_t) {
-        c->tl("T chain start (s2)", s2);
-        const bool tfill = tfill0;
-        c->tgen ^= 1;                        // the other generation of the temporal class arenas (gpcsd_ctx::tgen)
-        staged_chain_guard(c, s2);
-        if (tfill) temporal_fill(c, &hp, 1, t, nt, *sym_t, e.status + 1, 0, s2);
-        else make_kt(s2);
-        // staged whenever it applies: the T factors are then a launch of their own instead of riding in the leaf launch (same
-        // bits either way).  A consumer in the tridiagonal form gets stages 1 and 3 only; anybody else all four.
-        const bool staged = staged0;
-        clear_late_status(c, e.status, s2, staged && !tri_consumer);
-        {
-            ProfScope ps(c, "eigh_temporal", 9.0 * (double)nt * nt * nt, s2);
-            if (staged) {
-                // stage 1 (tridiagonalisation), then on this stream stage 2 (divide & conquer) and BESIDE it, on stream4, stage 3
-                // (T factors, Q), then stage 4 (back-transformation) behind both.  A log-likelihood in the tridiagonal form
-                // starts its tail behind stage 3 and never waits for stages 2 and 4.
-                const bool tri = tri_consumer;
-                int *late = e.status + gpcsd_ctx::STATUS_LATE;    // stages 2 and 4 report here (gpcsd_ctx::STATUS_LATE)
-                // stage 5 instead of stage 3: the tail publishes its progress, the caller's loglik_tri_pre queues the rest
-                const bool st5 = tri && q_stage5_applies(c, sym_t);                      // T, Q by stage 5's kernels
-                const bool pipe = st5 && q_pipe_applies(c, sym_t);                       // ... under the running stage 1
-                if (pipe) GP_HIP(hipEventRecord(c->ev_t0, s2));
-                c->pipe_req = st5 ? 1 : 0;
-                eigh_pair_device(c, nullptr, 0, nullptr, nullptr, nullptr, Kt, nt, e.et, e.Qt, sym_t, e.status + 1, s2, need_merged, 1, 0,
-                                 -1, 2, /*stage=*/1);
-                c->pipe_req = 0;
-                GP_HIP(hipEventRecord(c->ev_t1, s2));
-                if (!tri)
-                    eigh_pair_device(c, nullptr, 0, nullptr, nullptr, nullptr, Kt, nt, e.et, e.Qt, sym_t, late + 1, s2, need_merged, 1, 0,
-                                     -1, 2, /*stage=*/2);
-                {
-                    hipStream_t sq = c->stream4;
-                    if (pipe) {
-                        e.pipe_pending = true;
-                        e.pa.Kt = Kt; e.pa.nt = nt; e.pa.et = e.et; e.pa.Qt = e.Qt; e.pa.sym_t = sym_t; e.pa.status = e.status + 1;
-                        e.pa.need_merged = need_merged; e.pa.nT = 1; e.pa.stride = 0; e.pa.rep = 0; e.pa.q_gen = c->eig_gen[1];
-                        c->q_queued[c->tgen] = false;
-                        c->q_gen = -1;         // (until stage 5 is queued)
-                    } else {
-                        if (st5) {
-                            queue_stage5_plain(c, Kt, nt, e.et, e.Qt, sym_t, e.status + 1, need_merged, 1, 0);
-                        } else {
-                            GP_HIP(hipStreamWaitEvent(sq, c->ev_t1, 0));
-                            GP_HIP(hipStreamWaitEvent(sq, c->ev_pc, 0));      // (stream5's readers of the Q about to be rewritten)
-                            eigh_pair_device(c, nullptr, 0, nullptr, nullptr, nullptr, Kt, nt, e.et, e.Qt, sym_t, e.status + 1, sq,
-                                             need_merged, 1, 0, -1, 2, /*stage=*/3);
-                        }
-                        GP_HIP(hipEventRecord(c->ev_q[c->tgen], sq));
-                        c->q_queued[c->tgen] = true;
-                        c->q_gen = c->eig_gen[1];
-                    }
-                }
-                if (!tri) {
-                    GP_HIP(hipStreamWaitEvent(s2, c->ev_q[c->tgen], 0));
-                    eigh_pair_device(c, nullptr, 0, nullptr, nullptr, nullptr, Kt, nt, e.et, e.Qt, sym_t, late + 1, s2, need_merged, 1, 0,
-                                     -1, 2, /*stage=*/4);
-                }
-                e.tri = e.wait_q = tri;
-                c->decomp_t_full = !tri;
-            } else {
-                eigh_pair_device(c, nullptr, 0, nullptr, nullptr, nullptr, Kt, nt, e.et, e.Qt, sym_t, e.status + 1, s2, need_merged, 1, 0,
-                                 -1, tfill ? 2 : 0);
-                c->decomp_t_full = true;
-            }
-        }
-        GP_HIP(hipEventRecord(c->ev_join, s2));
-        c->tl("T chain end (s2)", s2);
+        // A consumer in the tridiagonal form gets stages 1 and 3 (or 5) only; anybody else all four.
+        tc.Kt = Kt; tc.et = e.et; tc.Qt = e.Qt; tc.hp = &hp; tc.t = t;
+        tc.need_merged = need_merged; tc.status = e.status;
+        tc.tri = tri_consumer; tc.x_via_tri_pre = x_via_tri_pre; tc.single = true;
+        tchain_begin(c, tc, make_kt);
+        tchain_finish(c, tc);
+        if (tc.tri) tchain_consumer(c, tc, e, 0, true);
+        c->decomp_t_full = !tc.tri;
         c->decomp_gen[1] = c->eig_gen[1];
         e.wait_temporal = true;
     }
@@ -752,8 +796,11 @@ EigState front_half(gpcsd_ctx *c, const gpcsd_hparams *hp, double jitter, bool n
         if (sfill) spatial_fill(c, Ks, nx, 0, 1, &jitter, *sym_s, e.status, 0, s3);
         {
             ProfScope ps(c, "eigh_spatial", 9.0 * (double)nx * nx * nx, s3);
-            eigh_pair_device(c, Ks, nx, e.es, e.Qs, sym_s, nullptr, 0, nullptr, nullptr, nullptr, e.status, s3, need_merged_s, 1, 0, -1,
-                             sfill ? 1 : 0);
+            EighCall r;
+            r.side[0] = {Ks, nx, e.es, e.Qs, sym_s, 1, /*prefolded=*/sfill};
+            r.status = e.status;
+            r.need_merged = need_merged_s;
+            eigh_pair_device(c, r, s3);
         }
         GP_HIP(hipEventRecord(c->ev_sjoin, s3));
         c->tl("S chain end (s3)", s3);

@@ -140,15 +140,8 @@ static int loglik_parts_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, double *out2
     const FoldMode fm0 = fold_mode(c, hp);                          // the decision; its views are of the previous generation
     const double *Yf = fm0.on ? folded_lfp(c, fm0) : nullptr;
     // (the spatial chain is joined by the tail: the tridiagonal form queues its first product in front of that wait)
-    c->q_pipe_want = fm0.on && fm0.ft.on;                           // (X = Y~ Q goes through loglik_tri_pre below: stage 5 may apply)
-    EigState e;
-    try {
-        e = front_half(c, hp, hp->jitter, !fm0.on, /*join_s=*/!fm0.on, /*want_tri=*/fm0.on);
-    } catch (...) {
-        c->q_pipe_want = false;
-        throw;
-    }
-    c->q_pipe_want = false;
+    // (X = Y~ Q goes through loglik_tri_pre below: stage 5 may apply)
+    EigState e = front_half(c, hp, hp->jitter, !fm0.on, /*join_s=*/!fm0.on, /*want_tri=*/fm0.on, -1, /*x_via_tri_pre=*/fm0.on && fm0.ft.on);
     const FoldMode fm = fold_mode(c, hp);                           // views of the generation the front half just launched
     const int nx = c->nx, nt = c->nt, R = c->ntrials;
     hipStream_t s = c->stream;
@@ -186,8 +179,8 @@ static int loglik_parts_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, double *out2
 // tridiagonalisation that should have been running beside it -- kernels serialised by a profiler or a debugger, an oversubscribed
 // card, a tail that could not get a CU.  The launch did nothing with the unfinished reflectors, so the evaluation is void, not
 // wrong.  The call that collects it switches the pipeline off for this context (latched: the conditions that made one gate miss
-// make the next one miss), counts it (gpcsd_q_pipeline_stats) and evaluates again: behind the END of the tail queue_stage5_plain
-// forms the same T, Q and X.  `piped`: the call was queued while the pipeline was on.
+// make the next one miss), counts it (gpcsd_q_pipeline_stats) and evaluates again: behind the END of the tail the unpipelined
+// stage 5 (tchain_finish) forms the same T, Q and X.  `piped`: the call was queued while the pipeline was on.
 static bool q_pipe_missed(gpcsd_ctx *c, int rc, bool piped) {
     if (rc != 7 || !piped) return false;
     c->q_pipe = false;
@@ -643,15 +636,8 @@ static int predict_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, 
         if (sz.ns > 0 && sz.ns + sz.na == nz) {
             // the chains go first (they need no upload of this call), then the host-side uploads
             const bool ptri = fm0.ft.on && predict_tridiag_applies(fm0.ft.ns, fm0.ft.na, c->ntrials);
-            c->q_pipe_want = ptri;                                          // (X = Y~ Q goes through loglik_tri_pre: stage 5 may apply)
-            EigState ef;
-            try {
-                ef = front_half(c, hp, 0.0, false, /*join_s=*/false, /*want_tri=*/ptri, fold_s ? -1 : 1);  // no jitter in predict (gpcsd1d.py:258)
-            } catch (...) {
-                c->q_pipe_want = false;
-                throw;
-            }
-            c->q_pipe_want = false;
+            // no jitter in predict (gpcsd1d.py:258); X = Y~ Q goes through loglik_tri_pre: stage 5 may apply
+            EigState ef = front_half(c, hp, 0.0, false, /*join_s=*/false, /*want_tri=*/ptri, fold_s ? -1 : 1, /*x_via_tri_pre=*/ptri);
             const FoldMode fm = fold_mode(c, hp, fold_s);
             const double *Yf = folded_lfp(c, fm);
             double *dzf = c->upload_cached<double>("pred_z", z, (size_t)nz * c->dim);
@@ -769,9 +755,10 @@ static bool same_temporal(const gpcsd_hparams *a, const gpcsd_hparams *b) {
 // Both sets decomposed, set b's results at replica b of the generation just started (folded-basis callers only).
 // pred_tri: the prediction (set 1) takes the tridiagonal form too, so that nobody reads the temporal spectrum or eigenvectors: the
 // staged temporal chain then stops behind stages 1 and 3.
+// x_via_tri_pre: the log-likelihood forms X = Y~ Q through loglik_tri_pre (a pipelined stage 5 may apply: TChain).
 // fold_s = false: the tails take the spatial side unfolded (merged eigenvectors; the eigensolver still folds it internally).
 static void front_half_pair(gpcsd_ctx *c, const gpcsd_hparams *const hp[2], const double jitter[2], PairFront &out, bool pred_tri,
-                            bool fold_s = true) {
+                            bool x_via_tri_pre, bool fold_s = true) {
     const Geo g = resident_geo(c);
     const int nx = c->nx, nt = c->nt;
     const long nxx = (long)nx * nx, ntt = (long)nt * nt;
@@ -785,7 +772,6 @@ static void front_half_pair(gpcsd_ctx *c, const gpcsd_hparams *const hp[2], cons
     const int nT = (same_temporal(hp[0], hp[1]) && (c->decomp_cache_on || (c->pair_share_x && !one_kt_off))) ? 1 : 2;
     double *scal = c->buf<double>("scal_status", gpcsd_ctx::RESULT_DOUBLES);
     int *status = reinterpret_cast<int *>(scal + gpcsd_ctx::SCAL_N);
-    int *late = status + gpcsd_ctx::STATUS_LATE;           // stages 2 and 4 of a staged temporal chain report here
     const bool clear_now = !c->status_zeroed && !c->async_pending;
     if (clear_now) GP_HIP(hipMemsetAsync(status, 0, gpcsd_ctx::STATUS_N * sizeof(int), s));
     c->status_zeroed = false;
@@ -801,71 +787,16 @@ static void front_half_pair(gpcsd_ctx *c, const gpcsd_hparams *const hp[2], cons
     // Gram matrices.  Temporal (stream2): replica b = Kt(hp[b]).  Spatial (stream3): replica b = Ks(hp[b]) + jitter[b] I; with
     // equal spatial hyper-parameters -- the usual pair -- the two differ by the diagonal shift only, so the matrix is
     // assembled once and copied (the same GEMM output plus the same diagonal add: the same bits).
-    const bool tfill = temporal_fill_applies(c, sym_t, nt, false);       // (the paired call is refused for host temporal Grams)
-    const bool staged = tfill && ll_tridiag_enabled(c) && eigh_stageable(sym_t, nt);
-    bool st5 = false, pipe = false;      // stage 5's kernels instead of stage 3's, and pipelined: decided in part 1
-    // part 1: the inputs and (staged) stage 1, or the whole chain; part 2 (staged only): stage 2, and stage 3 beside it
-    auto run_T = [&](int part) {
-        if (part == 1) {
-            c->tl("T chain start (s2)", s2);
-            c->tgen ^= 1;                    // the other generation of the temporal class arenas (gpcsd_ctx::tgen)
-            staged_chain_guard(c, s2);
-            clear_late_status(c, status, s2, staged && !pred_tri);
-            if (tfill) temporal_fill(c, hp, nT, t, nt, *sym_t, status + 1, 2, s2);
-            else for (int b = 0; b < nT; ++b) build_kt(c, hp[b], t, nt, t, nt, Kt + b * ntt, s2);
-        }
-        // the temporal chain is the critical path of the call: it is queued before the host spends its time on the launches of the
-        // spatial Gram assembly (status words [1], [3]; one replica when the problem is shared -- decomposition cache on, equal
-        // temporal hyper-parameters).  (All four problems in ONE chain was measured slower, 1.38 against 1.18 ms per cfg3 step: with
-        // two chains the log-likelihood's spatial projection runs under the end of the temporal one.)
-        {
-            ProfScope ps(c, part == 2 ? "eigh_temporal_stage2" : "eigh_temporal", part == 2 ? 0.0 : 9.0 * (double)nt * nt * nt * nT, s2);
-            if (staged && part == 1) {   // the log-likelihood's tail starts behind stages 1 + 3 (see front_half, EigState::tri)
-                // (only when the prediction takes the tridiagonal form too: a stage 4 behind stage 5 would read T factors summed in
-                // another order than stage 3's, and the pair would differ from its fenced calls in the last bits)
-                st5 = pred_tri && q_stage5_applies(c, sym_t);
-                pipe = st5 && q_pipe_applies(c, sym_t);
-                if (pipe) GP_HIP(hipEventRecord(c->ev_t0, s2));
-                c->pipe_req = st5 ? 1 : 0;
-                eigh_pair_device(c, nullptr, 0, nullptr, nullptr, nullptr, Kt, nt, et, Qt, sym_t, status + 1, s2, false, nT, 2, -1, 2, 1);
-                c->pipe_req = 0;
-                GP_HIP(hipEventRecord(c->ev_t1, s2));
-                c->tl("T stage 1 end (s2)", s2);
-                return;
-            }
-            if (staged) {
-                // stage 2 (divide & conquer) on the chain's stream; beside it, on stream4, stage 3 (T factors, Q); stage 4
-                // (back-transformation) behind both.  (Stage 3 on the main stream, in front of X: 1.14 against 1.10 ms -- the
-                // main stream is rarely idle when stage 1 ends.)  With the prediction in the tridiagonal form as well: stage 3 alone.
-                if (!pred_tri)
-                    eigh_pair_device(c, nullptr, 0, nullptr, nullptr, nullptr, Kt, nt, et, Qt, sym_t, late + 1, s2, false, nT, 2, -1, 2, 2);
-                hipStream_t sq = c->stream4;
-                if (pipe) {              // (stage 5 is queued by the log-likelihood's loglik_tri_pre: EigState::pipe_pending)
-                    c->q_queued[c->tgen] = false;
-                } else {
-                    if (st5) {
-                        queue_stage5_plain(c, Kt, nt, et, Qt, sym_t, status + 1, false, nT, 2);
-                    } else {
-                        GP_HIP(hipStreamWaitEvent(sq, c->ev_t1, 0));
-                        GP_HIP(hipStreamWaitEvent(sq, c->ev_pc, 0));      // (stream5's readers of the Q about to be rewritten)
-                        eigh_pair_device(c, nullptr, 0, nullptr, nullptr, nullptr, Kt, nt, et, Qt, sym_t, status + 1, sq, false, nT, 2, -1, 2, 3);
-                    }
-                    GP_HIP(hipEventRecord(c->ev_q[c->tgen], sq));
-                    c->tl("Q end", sq);
-                    c->q_queued[c->tgen] = true;
-                }
-                c->q_gen = -1;           // (replicas: not what a separate call's cache looks for)
-                if (!pred_tri) {
-                    GP_HIP(hipStreamWaitEvent(s2, c->ev_q[c->tgen], 0));
-                    eigh_pair_device(c, nullptr, 0, nullptr, nullptr, nullptr, Kt, nt, et, Qt, sym_t, late + 1, s2, false, nT, 2, -1, 2, 4);
-                }
-            } else {
-                eigh_pair_device(c, nullptr, 0, nullptr, nullptr, nullptr, Kt, nt, et, Qt, sym_t, status + 1, s2, false, nT, 2, -1,
-                                 tfill ? 2 : 0);
-            }
-        }
-        GP_HIP(hipEventRecord(c->ev_join, s2));
-        c->tl("T chain end (s2)", s2);
+    // The temporal chain is the critical path of the call: its first part is queued before the host spends its time on the launches
+    // of the spatial Gram assembly (status words [1], [3]; one replica when the problem is shared -- decomposition cache on, equal
+    // temporal hyper-parameters).  (All four problems in ONE chain was measured slower, 1.38 against 1.18 ms per cfg3 step: with
+    // two chains the log-likelihood's spatial projection runs under the end of the temporal one.)
+    TChain tc(c, sym_t, nt, /*host_kt=*/false);           // (the paired call is refused for host temporal Grams)
+    tc.Kt = Kt; tc.et = et; tc.Qt = Qt; tc.hp = hp; tc.t = t; tc.nT = nT;
+    tc.need_merged = false; tc.status = status; tc.stride = 2;
+    tc.tri = tc.staged && pred_tri; tc.x_via_tri_pre = x_via_tri_pre; tc.scope2 = "eigh_temporal_stage2";
+    auto build_kts = [&](hipStream_t st) {
+        for (int b = 0; b < nT; ++b) build_kt(c, hp[b], t, nt, t, nt, Kt + b * ntt, st);
     };
     const bool same_ks = hp[0]->R == hp[1]->R && hp[0]->ell_s[0] == hp[1]->ell_s[0] &&
                          (g.dim == 1 || (hp[0]->eps == hp[1]->eps && hp[0]->ell_s[1] == hp[1]->ell_s[1]));
@@ -897,8 +828,11 @@ static void front_half_pair(gpcsd_ctx *c, const gpcsd_hparams *const hp[2], cons
         // two replicas of the spatial problem on stream3 (status words [0], [2]) -- or the one both sets share
         {
             ProfScope ps(c, "eigh_spatial", 9.0 * (double)nx * nx * nx * nS, s3);
-            eigh_pair_device(c, Ks, nx, es, Qs, sym_s, nullptr, 0, nullptr, nullptr, nullptr, status, s3, /*need_merged=*/!fold_s, nS, 2, -1,
-                             sfill ? 1 : 0);
+            EighCall r;
+            r.side[0] = {Ks, nx, es, Qs, sym_s, nS, /*prefolded=*/sfill};
+            r.status = status; r.status_stride = 2;
+            r.need_merged = !fold_s;
+            eigh_pair_device(c, r, s3);
         }
         if (share_s) {                   // set 1's spectrum: set 0's shifted by the difference of the jitters, in replica 1's slots
             const double dj = jitter[1] - jitter[0];
@@ -913,12 +847,12 @@ static void front_half_pair(gpcsd_ctx *c, const gpcsd_hparams *const hp[2], cons
     static const bool s_first = getenv("GPCSD_S_FIRST") && getenv("GPCSD_S_FIRST")[0] == '1';     // (A/B: the spatial chain queued first)
     if (s_first) {
         run_S();
-        run_T(1);
+        tchain_begin(c, tc, build_kts);
     } else {
-        run_T(1);
+        tchain_begin(c, tc, build_kts);
         run_S();
     }
-    if (staged) run_T(2);
+    tchain_finish(c, tc);
     c->decomp_gen[0] = c->decomp_gen[1] = -1;          // replicas are not what the separate calls' cache looks for
     const double *d_sig[2] = {c->upload_cached<double>("sig2n", hp[0]->sig2n, 1), c->upload_cached<double>("sig2n_pair", hp[1]->sig2n, 1)};
     for (int b = 0; b < 2; ++b) {
@@ -934,16 +868,8 @@ static void front_half_pair(gpcsd_ctx *c, const gpcsd_hparams *const hp[2], cons
         e.wait_temporal = e.wait_spatial = true;
         e.d_sig = d_sig[b];
         e.nsig = 1;
-        if (staged && (b == 0 || pred_tri)) {      // set 0 is the log-likelihood's: replica 0 of the temporal classes
-            e.tri = e.wait_q = true;
-            e.tri_rep = bt;
-            e.tri_count = nT;
-            if (pipe && b == 0) {        // X with replica 0's Q: the log-likelihood's set
-                e.pipe_pending = true;
-                e.pa.Kt = Kt; e.pa.nt = nt; e.pa.et = et; e.pa.Qt = Qt; e.pa.sym_t = sym_t; e.pa.status = status + 1;
-                e.pa.need_merged = false; e.pa.nT = nT; e.pa.stride = 2; e.pa.rep = 0; e.pa.q_gen = -1;
-            }
-        }
+        // set 0 is the log-likelihood's: replica 0 of the temporal classes, and X with replica 0's Q
+        if (tc.staged && (b == 0 || pred_tri)) tchain_consumer(c, tc, e, bt, /*forms_x=*/b == 0);
         FoldMode &fm = out.fm[b];
         fm = fold_mode(c, hp[b], fold_s);               // replica 0 of the generations just started ...
         if (fm.fs.on) { fm.fs.w += (long)b * vs.sw; fm.fs.U += (long)bs * vs.sU; }      // ... moved to replica b
@@ -1037,19 +963,6 @@ static void pair_prefetch_drop(gpcsd_ctx *c) {
     c->pair_prefetch = nullptr;
 }
 
-// The paired front half with the promise that X = Y~ Q goes through loglik_tri_pre (stage 5 may apply)
-static void front_half_pair_q(gpcsd_ctx *c, const gpcsd_hparams *const hps[2], const double jit[2], PairFront &pf, const PairPlan &P,
-                              bool pipelined = true) {
-    c->q_pipe_want = P.fm0.ft.on && pipelined;
-    try {
-        front_half_pair(c, hps, jit, pf, P.pred_tri, P.fold_s);
-    } catch (...) {
-        c->q_pipe_want = false;
-        throw;
-    }
-    c->q_pipe_want = false;
-}
-
 // gpcsd_prefetch_pair: the caller knows the hyper-parameters of its NEXT paired call (a grid or a chain of proposals fixed in
 // advance, the replicas of a lock-step batch, a benchmark loop): the two decomposition chains of that call are queued NOW, on their own
 // streams, and start as soon as those streams are free -- typically while the current call's log-likelihood is still being
@@ -1071,7 +984,7 @@ extern "C" int gpcsd_prefetch_pair(gpcsd_ctx *c, const gpcsd_hparams *hp_ll, con
     PairPrefetch *pp = new PairPrefetch();
     try {
         // (not pipelined: the chain has a whole step's head start, T and Q follow it at once -- the same kernels, the same bits)
-        front_half_pair_q(c, hps, jit, pp->pf, P, /*pipelined=*/false);
+        front_half_pair(c, hps, jit, pp->pf, P.pred_tri, /*x_via_tri_pre=*/false, P.fold_s);
     } catch (...) {
         delete pp;
         throw;
@@ -1141,7 +1054,7 @@ extern "C" int gpcsd_loglik_predict_async(gpcsd_ctx *c, const gpcsd_hparams *hp_
         }
         pair_prefetch_drop(c);
     }
-    if (!taken) front_half_pair_q(c, hps, jit, pf, P);
+    if (!taken) front_half_pair(c, hps, jit, pf, P.pred_tri, /*x_via_tri_pre=*/P.fm0.ft.on, P.fold_s);
     const double *Yf = folded_lfp(c, pf.fm[1]);
     const long up0 = c->upload_count;
     double *dzf = c->upload_cached<double>("pred_z", z, (size_t)nz * c->dim);

@@ -129,7 +129,11 @@ static int loglik_grad_impl(gpcsd_ctx *c, const gpcsd_hparams *hps, int B, doubl
     }
     {
         ProfScope ps(c, "eigh_temporal", 9.0 * (double)nt * nt * nt * B, s2);
-        eigh_pair_device(c, nullptr, 0, nullptr, nullptr, nullptr, Kt, nt, et, Qt, sym_t, st + B, s2, !fold, B, 1, -1, tfill ? 2 : 0);
+        EighCall r;
+        r.side[1] = {Kt, nt, et, Qt, sym_t, B, /*prefolded=*/tfill};
+        r.status = st + B; r.status_stride = 1;
+        r.need_merged = !fold;
+        eigh_pair_device(c, r, s2);
     }
     GP_HIP(hipEventRecord(c->ev_join, s2));
     // Ks_b = A_b Kgl_b A_b^T + jitter_b I                     covariances.py:74-96 / :204-232
@@ -193,7 +197,11 @@ static int loglik_grad_impl(gpcsd_ctx *c, const gpcsd_hparams *hps, int B, doubl
             k_add_diag(c, Ks, nx, 0.0, s, tab, B, nxx);
         }
         ProfScope ps(c, "eigh_spatial", 9.0 * (double)nx * nx * nx * B, s);
-        eigh_pair_device(c, Ks, nx, es, Qs, sym_s, nullptr, 0, nullptr, nullptr, nullptr, st, s, !fold, B, 1, -1, sfill ? 1 : 0);
+        EighCall r;
+        r.side[0] = {Ks, nx, es, Qs, sym_s, B, /*prefolded=*/sfill};
+        r.status = st; r.status_stride = 1;
+        r.need_merged = !fold;
+        eigh_pair_device(c, r, s);
     }
     if (kron) {
         // the backward pass's hyper-parameter-only factors, queued here where the main stream would otherwise wait for the chains:

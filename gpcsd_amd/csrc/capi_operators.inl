@@ -178,18 +178,21 @@ extern "C" int gpcsd_kphig_2d(gpcsd_ctx *c, const double *xy, int nx, const doub
     GP_API_END(c)
 }
 
-extern "C" int gpcsd_eigh(gpcsd_ctx *c, const double *A, int n, double *evals, double *evecs) {
-    GP_API_BEGIN(c)
+static int eigh_impl(gpcsd_ctx *c, const double *A, int n, double *evals, double *evecs, bool claim_psd) {
     GP_REQUIRE(A && evals && evecs && n > 0, -3, "eigh: bad arguments");
     double *dA = c->upload<double>("op_in0", A, (size_t)n * n);
     double *dw = c->buf<double>("op_w", n);
     double *dV = c->buf<double>("op_out", (size_t)n * n);
     int *st = c->buf<int>("status", 4);
     GP_HIP(hipMemsetAsync(st, 0, 4 * sizeof(int), c->stream));
-    eigh_device(c, dA, n, dw, dV, st, c->stream, "eigh");
+    eigh_device(c, dA, n, dw, dV, st, c->stream, claim_psd);
     c->download(evals, dw, n * sizeof(double));
     c->download(evecs, dV, (size_t)n * n * sizeof(double));
     return finish_status(c, st);
+}
+extern "C" int gpcsd_eigh(gpcsd_ctx *c, const double *A, int n, double *evals, double *evecs) {
+    GP_API_BEGIN(c)
+    return eigh_impl(c, A, n, evals, evecs, /*claim_psd=*/false);
     GP_API_END(c)
 }
 
@@ -197,12 +200,9 @@ extern "C" int gpcsd_eigh(gpcsd_ctx *c, const double *A, int n, double *evals, d
 // way a caller's matrix may take the tridiagonalisation's rank-revealing early exit (gpcsd_tail_early_exit; n <= 192 only).
 extern "C" int gpcsd_eigh_psd(gpcsd_ctx *c, const double *A, int n, double *evals, double *evecs) {
     if (!c) return -3;
-    struct Claim {
-        gpcsd_ctx *c;
-        explicit Claim(gpcsd_ctx *cc) : c(cc) { c->claim_psd = true; }
-        ~Claim() { c->claim_psd = false; }
-    } claim(c);
-    return gpcsd_eigh(c, A, n, evals, evecs);
+    GP_API_BEGIN(c)
+    return eigh_impl(c, A, n, evals, evecs, /*claim_psd=*/true);
+    GP_API_END(c)
 }
 
 // `count` independent symmetric matrices of the same order in ONE chain of launches (the replicated-class machinery behind
@@ -217,7 +217,10 @@ extern "C" int gpcsd_eigh_batch(gpcsd_ctx *c, const double *A, int n, int count,
     double *dV = c->buf<double>("op_out", nn * count);
     int *st = c->buf<int>("status_batch", (size_t)count);
     GP_HIP(hipMemsetAsync(st, 0, (size_t)count * sizeof(int), c->stream));
-    eigh_pair_device(c, dA, n, dw, dV, nullptr, nullptr, 0, nullptr, nullptr, nullptr, st, c->stream, true, count, 1);
+    EighCall r;
+    r.side[0] = {dA, n, dw, dV, nullptr, count};
+    r.status = st; r.status_stride = 1;
+    eigh_pair_device(c, r, c->stream);
     c->download(evals, dw, (size_t)n * count * sizeof(double));
     c->download(evecs, dV, nn * count * sizeof(double));
     c->download(status, st, (size_t)count * sizeof(int));

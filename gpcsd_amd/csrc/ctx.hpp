@@ -213,7 +213,6 @@ struct gpcsd_ctx {
     // scaling pass fills the arena from a caller's matrix.  Only such a class may take the tridiagonalisation's rank-revealing early
     // exit (sytrd_regtail.hpp): the claim comes from the producer of the matrix, not from how the arena happened to be filled.
     std::map<std::string, bool> arena_psd;
-    bool claim_psd = false;                 // gpcsd_eigh_psd() in progress: the caller vouches that its matrix is positive semi-definite
     bool tail_early_exit = true;            // gpcsd_tail_early_exit() / GPCSD_TAIL_EARLY_EXIT=0: PSD classes may stop the tridiagonalisation early
     bool fault_stage2 = false;              // gpcsd_debug_fault_stage2(): test aid, the staged divide & conquer reports status 3
     bool gram_fp32 = false;                 // gpcsd_set_gram_precision(): Gram builders evaluate in float (cfg5 variant)
@@ -225,23 +224,16 @@ struct gpcsd_ctx {
     // panel; T factors and the finished columns of Q follow on stream4 WHILE the tail reduces the next panel, and the matching
     // columns of X = Y~ Q on the main stream behind an event per panel -- behind the tail only the last panel's share is left (T, Q
     // and X stood for 0.18 ms of a 0.95 ms cfg3 step).
-    // q_pipe: the switch (gpcsd_q_pipeline() / GPCSD_Q_PIPE=0).  q_pipe_want: set by a caller around its front half -- it promises to
-    // form X through loglik_tri_pre, where stage 5 is queued (EigState::pipe_pending).  pipe_req: set around the stage-1 call
-    // (problem set-up, graph key).  q_pipe_x: what stage 5 hangs on every finished block of columns -- in / out (nx R rows of nt), the
-    // parity blocks' first columns.
+    // q_pipe: the switch (gpcsd_q_pipeline() / GPCSD_Q_PIPE=0).  Everything else travels in the calls: a caller of front_half /
+    // front_half_pair promises (`x_via_tri_pre`) to form X through loglik_tri_pre, where stage 5 is queued (EigState::pipe_pending);
+    // the chain's one queuing routine (capi.hip: TChain) asks stage 1 for progress words (EighCall::progress); queue_q_pipeline
+    // hands stage 5 what it hangs on every finished block of columns (EighCall::x).
     // gpcsd_prefetch_pair (capi_fused.inl): the next paired call's front half, queued ahead of that call (PairPrefetch, owned here;
     // dropped by any other front half)
     void *pair_prefetch = nullptr;
     long pair_prefetch_queued = 0, pair_prefetch_taken = 0;
     bool q_pipe = true;
-    bool q_pipe_want = false;
-    int pipe_req = 0;
     long q_pipe_calls = 0;
-    struct QPipeX {
-        const double *in = nullptr;
-        double *out = nullptr;
-        int M = 0, ld = 0, c0[2] = {0, 0}, rep = 0;
-    } q_pipe_x;
     hipEvent_t ev_t0 = nullptr;             // the temporal chain's inputs are in place (stream2, in front of stage 1): stage 5 starts behind it
     bool t1_wait_pending = false;           // stage 5 was queued: the main stream's first reader of d / e still has to wait for ev_t1
     hipEvent_t ev_stage[8] = {};            // stage 5: panel k's columns of Q are final (stream4) -> the main stream's product on them

@@ -20,8 +20,7 @@
 
 namespace gpcsd {
 
-void eigh_large_multi(gpcsd_ctx *c, const EigReq *reqs, int nclass, int *d_status, int status_stride, hipStream_t s,
-                      int stage = 0);   // eigh_dc.hip
+void eigh_large_multi(gpcsd_ctx *c, const EigReq *reqs, int nclass, const EighCall &r, hipStream_t s);   // eigh_dc.hip
 
 // blockIdx.x = replica: inputs sA apart, eigenvalues sw apart, eigenvectors sZ apart, status words status_stride apart
 template <int NT>
@@ -332,13 +331,9 @@ FoldView eigh_fold_view(gpcsd_ctx *c, int slot, const SymDev *sy, int n, int cou
 static const char *const FOLD_TAGS[2][2][3] = {{{"p0", "p0s", "p0a"}, {"p0", "p0s", "p0a"}}, {{"p1", "p1s", "p1a"}, {"p1g", "p1gs", "p1ga"}}};
 const char *const *eigh_fold_tags(const gpcsd_ctx *c, int slot) { return &FOLD_TAGS[slot ? 1 : 0][slot ? (c->tgen & 1) : 0][1]; }
 
-static void eigh_pair_enqueue(gpcsd_ctx *c, double *A0, int n0, double *w0, double *Z0, const SymDev *sym0, double *A1, int n1,
-                              double *w1, double *Z1, const SymDev *sym1, int *d_status, hipStream_t s, bool need_merged,
-                              int count, int status_stride, int count1, int prefolded_mask, int stage) {
-    const int cnt[2] = {count, count1 > 0 ? count1 : count};      // replicas of problem 0 / problem 1
-    double *A[2] = {A0, A1}, *w[2] = {w0, w1}, *Z[2] = {Z0, Z1};
-    const int n[2] = {n0, n1};
-    const SymDev *sym[2] = {sym0, sym1};
+// (r: normalised by eigh_pair_device -- both replica counts >= 1)
+static void eigh_pair_enqueue(gpcsd_ctx *c, const EighCall &r, hipStream_t s) {
+    const int stage = r.stage;
     EigReq large[MAX_EIG_BATCH];
     int nlarge = 0;
     struct Fold {
@@ -348,7 +343,7 @@ static void eigh_pair_enqueue(gpcsd_ctx *c, double *A0, int n0, double *w0, doub
     const char *const *tags[2] = {FOLD_TAGS[0][0], FOLD_TAGS[1][c->tgen & 1]};     // [problem] -> {whole, symmetric, antisymmetric}
     // A small problem next to a large one rides along in the large problem's launches for free (GPCSD1D: 24 electrodes
     // next to 500 time points), instead of a serial 250 us single-workgroup Jacobi in front of them.
-    const bool pair_has_large = !force_jacobi() && (n0 > JACOBI_LDS_MAX || n1 > JACOBI_LDS_MAX);
+    const bool pair_has_large = !force_jacobi() && (r.side[0].n > JACOBI_LDS_MAX || r.side[1].n > JACOBI_LDS_MAX);
     auto submit = [&](double *Am, int nm, double *wm, double *Zm, const char *tag, long sA, long sw, long sZ, int nrep,
                       bool prefilled = false) {
         if (nm <= 0) return;
@@ -358,58 +353,87 @@ static void eigh_pair_enqueue(gpcsd_ctx *c, double *A0, int n0, double *w0, doub
         q.prefilled = prefilled;
         const bool small = nm <= JACOBI_LDS_MAX && !(pair_has_large && nm >= EIG_BATCH_MIN_N);
         GP_REQUIRE(!prefilled || !(small || force_jacobi()), -3, "eigh: a prefilled class must take the tridiagonalisation path (n=%d)", nm);
-        if (small || force_jacobi()) eigh_jacobi(c, q, d_status, status_stride, s);
+        if (small || force_jacobi()) eigh_jacobi(c, q, r.status, r.status_stride, s);
         else large[nlarge++] = q;
     };
     for (int p = 0; p < 2; ++p) {
-        if (n[p] <= 0) continue;
-        const SymDev *sy = sym[p];
-        const long nn = (long)n[p] * n[p];
-        if (fold_applies(sy, n[p])) {
+        const EighSide &sd = r.side[p];
+        if (sd.n <= 0) continue;
+        const SymDev *sy = sd.sym;
+        const long nn = (long)sd.n * sd.n;
+        if (fold_applies(sy, sd.n)) {
             const int ns = sy->ns, na = sy->na;
             const std::string T = std::string("fold_") + tags[p][0] + "_";
-            double *Ks = c->buf<double>(T + "Ks", (size_t)ns * ns * cnt[p]),
-                   *Ka = c->buf<double>(T + "Ka", (size_t)std::max(na, 1) * na * cnt[p]);
-            const FoldView fv = eigh_fold_view(c, p, sy, n[p], cnt[p]);
+            double *Ks = c->buf<double>(T + "Ks", (size_t)ns * ns * sd.count),
+                   *Ka = c->buf<double>(T + "Ka", (size_t)std::max(na, 1) * na * sd.count);
+            const FoldView fv = eigh_fold_view(c, p, sy, sd.n, sd.count);
             fold[p].on = true;
             fold[p].ws = fv.w;
             fold[p].Us = fv.U;
             fold[p].wa = fv.w + ns;
             fold[p].Ua = fv.U + (size_t)ns * ns;
-            const bool pre = ((prefolded_mask >> p) & 1) || stage >= 2;     // the scaled halves are in the class arenas already
+            const bool pre = sd.prefolded || stage >= 2;     // the scaled halves are in the class arenas already
             if (!pre)
-                hipLaunchKernelGGL(sym_fold_kernel, dim3(ceil_div((long)ns * ns, 256), cnt[p]), dim3(256), 0, s, (const double *)A[p],
-                                   n[p], *sy, Ks, Ka);
-            submit(Ks, ns, fold[p].ws, fold[p].Us, tags[p][1], (long)ns * ns, fv.sw, fv.sU, cnt[p], pre);
-            submit(Ka, na, fold[p].wa, fold[p].Ua, tags[p][2], (long)na * na, fv.sw, fv.sU, cnt[p], pre);
+                hipLaunchKernelGGL(sym_fold_kernel, dim3(ceil_div((long)ns * ns, 256), sd.count), dim3(256), 0, s, (const double *)sd.A,
+                                   sd.n, *sy, Ks, Ka);
+            submit(Ks, ns, fold[p].ws, fold[p].Us, tags[p][1], (long)ns * ns, fv.sw, fv.sU, sd.count, pre);
+            submit(Ka, na, fold[p].wa, fold[p].Ua, tags[p][2], (long)na * na, fv.sw, fv.sU, sd.count, pre);
         } else {
             GP_REQUIRE(stage == 0, -3, "eigh: staged solves need symmetry-folded problems (problem %d)", p);
-            GP_REQUIRE(!((prefolded_mask >> p) & 1), -3, "eigh: problem %d was announced as prefolded but symmetry folding does not apply", p);
-            submit(A[p], n[p], w[p], Z[p], tags[p][0], nn, n[p], nn, cnt[p]);
+            GP_REQUIRE(!sd.prefolded, -3, "eigh: problem %d was announced as prefolded but symmetry folding does not apply", p);
+            submit(sd.A, sd.n, sd.w, sd.Z, tags[p][0], nn, sd.n, nn, sd.count);
         }
     }
-    if (nlarge) eigh_large_multi(c, large, nlarge, d_status, status_stride, s, stage);
+    if (nlarge) eigh_large_multi(c, large, nlarge, r, s);
     // need_merged == false: the caller stays in the folded basis (eigh_fold_view) and never reads w / Z of a folded problem
     for (int p = 0; p < 2; ++p)
-        if (fold[p].on && need_merged && (stage == 0 || stage == 4))
-            hipLaunchKernelGGL(sym_unfold_kernel, dim3(n[p], cnt[p]), dim3(256), 0, s, n[p], *sym[p], (const double *)fold[p].ws,
-                               (const double *)fold[p].Us, (const double *)fold[p].wa, (const double *)fold[p].Ua, w[p], Z[p]);
+        if (fold[p].on && r.need_merged && (stage == 0 || stage == 4))
+            hipLaunchKernelGGL(sym_unfold_kernel, dim3(r.side[p].n, r.side[p].count), dim3(256), 0, s, r.side[p].n, *r.side[p].sym,
+                               (const double *)fold[p].ws, (const double *)fold[p].Us, (const double *)fold[p].wa,
+                               (const double *)fold[p].Ua, r.side[p].w, r.side[p].Z);
     GP_HIP(hipGetLastError());
+}
+
+// What a captured graph of a request depends on: EVERY field of the request, the stream, and the context state its launches read
+// besides -- the generation of each slot (gpcsd_ctx::par picks the fold-order output buffers, gpcsd_ctx::tgen the temporal class
+// arenas), SytrdProb::psd of the prefilled classes (a kernel argument: what their fills announced in gpcsd_ctx::arena_psd, and
+// the context's switch), and profiling mode 3, whose graphs carry clock stamps.  A field added to EighCall is added here.
+static std::string graph_key(const gpcsd_ctx *c, const EighCall &r, hipStream_t s) {
+    char key[512];
+    int nk = 0;
+    int psd_sig = 0;
+    for (int p = 0; p < 2; ++p) {
+        const EighSide &sd = r.side[p];
+        nk += snprintf(key + nk, sizeof(key) - nk, "%p|%d|%p|%p|%p|%d|%d|%d|", (void *)sd.A, sd.n, (void *)sd.w, (void *)sd.Z,
+                       (void *)(sd.sym ? sd.sym->rep_i : nullptr), sd.sym ? sd.sym->ns : 0, sd.count, (int)sd.prefolded);
+        const char *const *tg = eigh_fold_tags(c, p);
+        for (int h = 0; h < 2; ++h) {
+            const auto it = c->arena_psd.find(tg[h]);
+            if (sd.prefolded && it != c->arena_psd.end() && it->second) psd_sig |= 1 << (2 * p + h);
+        }
+    }
+    nk += snprintf(key + nk, sizeof(key) - nk, "%p|%d|%d|%d|%d|%d|x%p|%p|%d|%d|%d|%d|%d|", (void *)r.status, r.status_stride,
+                   (int)r.need_merged, r.stage, (int)r.progress, (int)r.claim_psd, (const void *)r.x.in, (void *)r.x.out, r.x.M, r.x.ld,
+                   r.x.c0[0], r.x.c0[1], r.x.rep);
+    snprintf(key + nk, sizeof(key) - nk, "%p|%d%d%d|%d|%d|%d", (void *)s, c->par[0], c->par[1], c->tgen & 1, (int)(c->prof_mode == 3),
+             (int)c->tail_early_exit, psd_sig);
+    return key;
 }
 
 // The large-n path is hundreds of dependent launches with nothing decided on the host (deflation counts stay on the
 // device), so it replays as a hipGraph: first call eager (allocates workspaces), second call captured, later calls
 // replayed.  A graph is retired whenever any context buffer is (re)allocated, since it holds raw device pointers.
-void eigh_pair_device(gpcsd_ctx *c, double *A0, int n0, double *w0, double *Z0, const SymDev *sym0, double *A1, int n1,
-                      double *w1, double *Z1, const SymDev *sym1, int *d_status, hipStream_t s, bool need_merged, int count,
-                      int status_stride, int count1, int prefolded_mask, int stage) {
-    if (count < 1) count = 1;
-    if (count1 < 1) count1 = count;
-    if (stage < 2) {                           // (stages 2, 3 and 4 continue the solve stage 1 started)
+void eigh_pair_device(gpcsd_ctx *c, const EighCall &req, hipStream_t s) {
+    EighCall r = req;
+    r.side[0].count = std::max(r.side[0].count, 1);
+    if (r.side[1].count < 1) r.side[1].count = r.side[0].count;
+    const int n0 = r.side[0].n, n1 = r.side[1].n;
+    if (r.stage < 2) {                         // (stages 2, 3 and 4 continue the solve stage 1 started)
         if (n0 > 0) ++c->eig_gen[0];           // whatever a previous call left in this slot's outputs is about to be replaced
         if (n1 > 0) ++c->eig_gen[1];
     }
     // the limit applies to what the solver actually factorises: a symmetry-folded problem is two half-size ones
+    const SymDev *sym0 = r.side[0].sym, *sym1 = r.side[1].sym;
     const int m0 = fold_applies(sym0, n0) ? std::max(sym0->ns, sym0->na) : n0;
     const int m1 = fold_applies(sym1, n1) ? std::max(sym1->ns, sym1->na) : n1;
     // (GPCSD_EIGH=jacobi, the single-workgroup cross-check, keeps its own smaller limit)
@@ -421,30 +445,11 @@ void eigh_pair_device(gpcsd_ctx *c, double *A0, int n0, double *w0, double *Z0, 
     // profiling mode 3 keeps replaying graphs, so the outer scopes time the chains as they run in production
     const bool prof_graph = c->prof_mode == 3;
     // (stage 5 records events and queues products on the main stream between its launches: never captured)
-    if (!any_large || (c->prof_on && !prof_graph) || !graphs_enabled() || stage == 5) {
-        eigh_pair_enqueue(c, A0, n0, w0, Z0, sym0, A1, n1, w1, Z1, sym1, d_status, s, need_merged, count, status_stride, count1, prefolded_mask, stage);
+    if (!any_large || (c->prof_on && !prof_graph) || !graphs_enabled() || r.stage == 5) {
+        eigh_pair_enqueue(c, r, s);
         return;
     }
-    // (the generation of each slot picks the fold-order output buffers, which are not among the arguments)
-    // (... and SytrdProb::psd of the prefilled classes, a kernel argument: what their fills announced, and the context's switch)
-    int psd_sig = (c->tail_early_exit ? 16 : 0) | (c->claim_psd ? 32 : 0) |
-                  (c->pipe_req ? 128 : 0);                                                           // (progress words: a kernel argument)
-    for (int p = 0; p < 2; ++p) {
-        const char *const *tg = eigh_fold_tags(c, p);
-        for (int h = 0; h < 2; ++h) {
-            const auto it = c->arena_psd.find(tg[h]);
-            if (((prefolded_mask >> p) & 1) && it != c->arena_psd.end() && it->second) psd_sig |= 1 << (2 * p + h);
-        }
-    }
-    char key[448];
-    const gpcsd_ctx::QPipeX qx = stage == 5 ? c->q_pipe_x : gpcsd_ctx::QPipeX();       // (stage 5 launches the caller's products)
-    int nk = snprintf(key, sizeof(key), "x%p|%p|%d|%d|%d|%d|%d|", (const void *)qx.in, (void *)qx.out, qx.M, qx.ld, qx.c0[0], qx.c0[1], qx.rep);
-    snprintf(key + nk, sizeof(key) - nk, "eigh|%p|%d|%p|%p|%p|%d|%p|%d|%p|%p|%p|%d|%p|%p|%d|%d|%d|%d%d|%d|%d|%d|%d|%d", (void *)A0, n0, (void *)w0, (void *)Z0,
-             (void *)(sym0 ? sym0->rep_i : nullptr), sym0 ? sym0->ns : 0, (void *)A1, n1, (void *)w1, (void *)Z1,
-             (void *)(sym1 ? sym1->rep_i : nullptr), sym1 ? sym1->ns : 0, (void *)d_status, (void *)s, (int)need_merged, count,
-             status_stride, c->par[0], c->par[1], count1, prefolded_mask, (int)(c->prof_mode == 3),   // (mode 3 graphs carry clock stamps)
-             stage + 8 * (c->tgen & 1), psd_sig);                                     // (the generation picks the temporal arenas)
-    gpcsd_ctx::GraphSlot &g = c->graphs[key];
+    gpcsd_ctx::GraphSlot &g = c->graphs[graph_key(c, r, s)];
     if (g.exec && g.epoch == c->alloc_epoch) {
         GP_HIP(hipGraphLaunch(g.exec, s));
         return;
@@ -458,7 +463,7 @@ void eigh_pair_device(gpcsd_ctx *c, double *A0, int n0, double *w0, double *Z0, 
         GP_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         c->capturing = true;
         try {
-            eigh_pair_enqueue(c, A0, n0, w0, Z0, sym0, A1, n1, w1, Z1, sym1, d_status, s, need_merged, count, status_stride, count1, prefolded_mask, stage);
+            eigh_pair_enqueue(c, r, s);
         } catch (...) {
             c->capturing = false;
             (void)hipStreamEndCapture(s, &graph);
@@ -477,18 +482,20 @@ void eigh_pair_device(gpcsd_ctx *c, double *A0, int n0, double *w0, double *Z0, 
             return;
         }
     }
-    eigh_pair_enqueue(c, A0, n0, w0, Z0, sym0, A1, n1, w1, Z1, sym1, d_status, s, need_merged, count, status_stride, count1, prefolded_mask, stage);
+    eigh_pair_enqueue(c, r, s);
     g.seen_epoch = c->alloc_epoch;
 }
 
-void eigh_device(gpcsd_ctx *c, double *A, int n, double *evals, double *evecs, int *d_status, hipStream_t s,
-                 const char *tag) {
+void eigh_device(gpcsd_ctx *c, double *A, int n, double *evals, double *evecs, int *d_status, hipStream_t s, bool claim_psd) {
     GP_REQUIRE(n >= 1, -3, "eigh: n=%d must be positive", n);
     GP_REQUIRE(n <= (force_jacobi() ? JACOBI_MAX_N : EIG_MAXN), GPCSD_ERR_CAPACITY,
                "eigh: matrix order %d exceeds the eigensolver's capacity of %d rows (GPCSD_MAX_EIG_N)", n,
                force_jacobi() ? JACOBI_MAX_N : EIG_MAXN);
-    (void)tag;
-    eigh_pair_device(c, A, n, evals, evecs, nullptr, nullptr, 0, nullptr, nullptr, nullptr, d_status, s, true, 1, 0, -1, 0, 0);
+    EighCall r;
+    r.side[0] = {A, n, evals, evecs};
+    r.status = d_status;
+    r.claim_psd = claim_psd;
+    eigh_pair_device(c, r, s);
 }
 
 }  // namespace gpcsd

@@ -437,7 +437,8 @@ double *eigh_Q_view(gpcsd_ctx *c, const char *tag, int n, int count) {
     return c->buf<double>(std::string("eig_") + tag + "_Q", (size_t)n * n * std::max(count, 1));
 }
 
-static void prep_problem(gpcsd_ctx *c, EigProb &p, hipStream_t s) {
+// claim_psd / progress: EighCall's
+static void prep_problem(gpcsd_ctx *c, EigProb &p, bool claim_psd, bool progress) {
     const int n = p.n;
     p.sp.n = n;
     {
@@ -448,11 +449,10 @@ static void prep_problem(gpcsd_ctx *c, EigProb &p, hipStream_t s) {
     // positive semi-definite only on the word of whoever filled the arena (EigArenaView::psd); the library's own scaling pass
     // copies a caller's matrix, about which nothing is known
     bool &psd = c->arena_psd[p.tag];
-    if (!p.prefilled) psd = c->claim_psd;         // (... unless the caller vouches for it: gpcsd_eigh_psd)
+    if (!p.prefilled) psd = claim_psd;            // (... unless the caller vouches for it: gpcsd_eigh_psd)
     p.sp.psd = (psd && c->tail_early_exit) ? 1 : 0;
-    // progress words on the word of the caller (gpcsd_ctx::pipe_req: stage 5 of a staged chain follows on another stream)
-    p.sp.pipe = (c->pipe_req && p.sp.k_tail == 0) ? 1 : 0;
-    (void)s;
+    // progress words on the word of the caller (EighCall::progress: stage 5 of a staged chain follows on another stream)
+    p.sp.pipe = (progress && p.sp.k_tail == 0) ? 1 : 0;
 }
 
 // scaling, copy into the ping-pong buffer and zeroing of the reflector storage for ALL problems in two launches
@@ -530,16 +530,15 @@ __global__ __launch_bounds__(256) void scale_copy_zero_batch_kernel(PrepBatch b)
     for (long i = i0; i < n + WY_NB + 2; i += stride) P.tau[i] = 0.0;     // (+2: the progress word)
 }
 
-static PrepBatch prep_batch_launch(gpcsd_ctx *c, EigProb *probs, int nclass, hipStream_t s, int *d_status = nullptr,
-                                   int status_stride = 0, bool launch = true) {
+static PrepBatch prep_batch_launch(gpcsd_ctx *c, EigProb *probs, int nclass, hipStream_t s, const EighCall &r = EighCall()) {
     PrepBatch pb{};
-    pb.status = d_status;
-    pb.status_stride = status_stride;
+    pb.status = r.status;
+    pb.status_stride = r.status_stride;
     int total = 0;
     for (int i = 0; i < MAX_BATCH; ++i) {
         pb.start[i] = total;
         if (i >= nclass) continue;
-        prep_problem(c, probs[i], s);
+        prep_problem(c, probs[i], r.claim_psd, r.progress);
         pb.A[i] = probs[i].A;
         pb.sA[i] = probs[i].sA;
         pb.amax[i] = probs[i].amax;
@@ -552,7 +551,7 @@ static PrepBatch prep_batch_launch(gpcsd_ctx *c, EigProb *probs, int nclass, hip
     pb.start[MAX_BATCH] = total;
     bool any = false;
     for (int i = 0; i < nclass; ++i) any = any || !probs[i].prefilled;
-    if (any && launch) {                        // (every class prefilled: the chain starts at the tridiagonalisation)
+    if (any && r.stage < 2) {                   // (every class prefilled: the chain starts at the tridiagonalisation)
         hipLaunchKernelGGL(absmax_partial_batch_kernel, dim3(AMAX_PARTS, total), dim3(256), 0, s, pb);
         hipLaunchKernelGGL(scale_copy_zero_batch_kernel, dim3(128, total), dim3(256), 0, s, pb);
         GP_HIP(hipGetLastError());
@@ -591,7 +590,9 @@ __global__ void fault_status_kernel(int *status, int stride, int count) {
     for (int r = threadIdx.x; r < count; r += blockDim.x) atomicMax(status + (long)r * stride, 3);
 }
 
-void eigh_large_batch(gpcsd_ctx *c, EigProb *probs, int nclass, int *d_status, int status_stride, hipStream_t s, int stage = 0) {
+void eigh_large_batch(gpcsd_ctx *c, EigProb *probs, int nclass, const EighCall &r, hipStream_t s) {
+    const int stage = r.stage, status_stride = r.status_stride;
+    int *const d_status = r.status;
     GP_REQUIRE(nclass >= 1 && nclass <= MAX_BATCH, -3, "eigh: %d problem classes outside [1,%d]", nclass, MAX_BATCH);
     int nmax = 0;
     bool replicated = false;
@@ -600,7 +601,7 @@ void eigh_large_batch(gpcsd_ctx *c, EigProb *probs, int nclass, int *d_status, i
         nmax = std::max(nmax, probs[i].n);
         replicated = replicated || probs[i].count > 1;
     }
-    const PrepBatch pb = prep_batch_launch(c, probs, nclass, s, d_status, status_stride, /*launch=*/stage < 2);
+    const PrepBatch pb = prep_batch_launch(c, probs, nclass, s, r);
     if (stage < 2) {
         ProfScope ps(c, "eigh_sytrd", 0.0, s);
         sytrd_batch_launch(c, sytrd_batch_of(pb), nclass, nmax, s);
@@ -623,7 +624,7 @@ void eigh_large_batch(gpcsd_ctx *c, EigProb *probs, int nclass, int *d_status, i
     if (stage == 1) return;                    // the tridiagonalisation alone
     if (stage == 5) {
         // Stage 3 panel by panel beside a stage 1 that is still running (wy.hip: wy_q_pipeline; the tails were launched with
-        // SytrdProb::pipe), each finished block of columns of Q followed by the caller's product on it (gpcsd_ctx::q_pipe_x).
+        // SytrdProb::pipe), each finished block of columns of Q followed by the caller's product on it (EighCall::x).
         ProfScope ps(c, "eigh_stage5_TQX", 0.0, s);
         WyBatch wq = wb;
         wq.status = d_status;
@@ -635,7 +636,7 @@ void eigh_large_batch(gpcsd_ctx *c, EigProb *probs, int nclass, int *d_status, i
             wq.p[i].sZ = (long)probs[i].n * probs[i].n;
             wq.p[i].w_scale = nullptr;
         }
-        const gpcsd_ctx::QPipeX x = c->q_pipe_x;
+        const QPipeX &x = r.x;
         GP_REQUIRE(!x.in || nclass <= 2, -3, "eigh: stage 5 with a product serves one folded problem (two classes)");
         int stage_k = 0, maxP = 0;
         for (int i = 0; i < nclass; ++i) maxP = std::max(maxP, wq.p[i].npanels);
@@ -757,7 +758,7 @@ void eigh_large_batch(gpcsd_ctx *c, EigProb *probs, int nclass, int *d_status, i
     GP_HIP(hipGetLastError());
 }
 
-void eigh_large_multi(gpcsd_ctx *c, const EigReq *reqs, int nclass, int *d_status, int status_stride, hipStream_t s, int stage) {
+void eigh_large_multi(gpcsd_ctx *c, const EigReq *reqs, int nclass, const EighCall &r, hipStream_t s) {
     static_assert(MAX_EIG_BATCH <= MAX_BATCH, "batch limits");
     GP_REQUIRE(nclass >= 1 && nclass <= MAX_BATCH, -3, "eigh: %d problem classes outside [1,%d]", nclass, MAX_BATCH);
     EigProb probs[MAX_BATCH];
@@ -768,7 +769,7 @@ void eigh_large_multi(gpcsd_ctx *c, const EigReq *reqs, int nclass, int *d_statu
         probs[i].sA = reqs[i].sA; probs[i].sw = reqs[i].sw; probs[i].sZ = reqs[i].sZ;
         probs[i].prefilled = reqs[i].prefilled;
     }
-    eigh_large_batch(c, probs, nclass, d_status, status_stride, s, stage);
+    eigh_large_batch(c, probs, nclass, r, s);
 }
 
 }  // namespace gpcsd

@@ -177,8 +177,9 @@ void k_unfold_swap_sum(gpcsd_ctx *c, const double *in, int C, double *list, long
 // ---------------------------------------------------------------- eigensolver (eigh.hip)
 // Symmetric eigendecomposition of A (n,n) on device.  evals ascending; evecs (n,n) row-major with
 // eigenvectors in COLUMNS (numpy.linalg.eigh convention).  A is destroyed.  status: device int (0 ok).
+// claim_psd: the caller vouches that A is positive semi-definite (EighCall::claim_psd)
 void eigh_device(gpcsd_ctx *c, double *A, int n, double *evals, double *evecs, int *d_status, hipStream_t s,
-                 const char *tag);
+                 bool claim_psd = false);
 constexpr int MAX_EIG_BATCH = 4;
 // One CLASS of eigenproblems: `count` replicas of the same order n whose inputs / outputs sit a fixed stride apart
 // (replica r reads A + r*sA, writes w + r*sw and Z + r*sZ).  The launches of a chain are shared by up to MAX_EIG_BATCH
@@ -238,25 +239,45 @@ __device__ __forceinline__ void class_of(const int *start, int g, int &cls, int 
     rep = g - start[cls];
 }
 // Two independent problems at once (Ks and Kt of one likelihood evaluation): every stage is batched so they share
-// launches; with a known symmetry each splits into two half-size problems first.  Either n may be <= 0 to skip.
-// need_merged = false: a caller that stays in the folded basis (eigh_fold_view) skips the unfold + rank merge of folded problems
-// count > 1: `count` replicas of both problems (inputs n*n apart, eigenvalues n apart, eigenvectors n*n apart); replica r
-// reports numerical failure in d_status[r * status_stride] (status_stride 0: one shared word)
-// prefolded_mask bit p: the folded halves of problem p are already in their class arenas, scaled (see EigArenaView); A_p is
-// then not read (symmetry folding must apply to that problem: eigh_fold_view(...).on)
-// stage: 0 = the whole solve.  Staged (capi_fused.inl: the log-likelihood's shifted tridiagonal systems need the temporal side
-// only as far as A / amax = Q T Q^T), same arguments every time:
-//   1 = the tridiagonalisation (chain stream);
-//   3 = the T factors of its reflector panels and the orthogonal factor Q itself (eigh_Q_view; T in EigArenaView::d / e) -- on
-//       ANY stream behind stage 1: it reads the reflectors, which stages 2 and 4 leave alone;
-//   2 = the divide & conquer of the tridiagonal matrix (chain stream, behind stage 1);
-//   4 = the back-transformation (chain stream, behind stage 2 AND stage 3: it needs the T factors).
-// Staged solves need folded (prefolded or not), tridiagonalisation-path problems within the fused back-transformation's size
-// (eigh_stageable).
-void eigh_pair_device(gpcsd_ctx *c, double *A0, int n0, double *w0, double *Z0, const SymDev *sym0, double *A1, int n1,
-                      double *w1, double *Z1, const SymDev *sym1, int *d_status, hipStream_t s, bool need_merged = true,
-                      int count = 1, int status_stride = 0, int count1 = -1,   // count1 > 0: replicas of problem 1 (else = count)
-                      int prefolded_mask = 0, int stage = 0);
+// launches; with a known symmetry each splits into two half-size problems first.  Everything a solve depends on travels in the
+// request (and from there into the graph key, eigh.hip): nothing is read from switches set around the call.
+struct EighSide {
+    double *A = nullptr;             // (n, n) per replica, destroyed; replicas n*n apart (eigenvalues n apart, eigenvectors n*n apart)
+    int n = 0;                       // <= 0: the side is absent
+    double *w = nullptr, *Z = nullptr;
+    const SymDev *sym = nullptr;
+    int count = 0;                   // replicas; < 1: one for side 0, as many as side 0 for side 1
+    bool prefolded = false;          // the folded halves are in their class arenas already, scaled (EigArenaView); A is not read
+};
+// what stage 5 hangs on every finished block of columns of Q: out[:, block] = in Q[:, block] on the main stream -- in / out (M rows
+// of ld), the parity blocks' first columns, the replica whose Q it is.  in == nullptr: Q only.
+struct QPipeX {
+    const double *in = nullptr;
+    double *out = nullptr;
+    int M = 0, ld = 0, c0[2] = {0, 0}, rep = 0;
+};
+struct EighCall {
+    EighSide side[2];                // [0] the first / spatial slot, [1] the second / temporal slot
+    int *status = nullptr;           // replica r reports numerical failure in status[r * status_stride] (stride 0: one shared word)
+    int status_stride = 0;
+    // false: a caller that stays in the folded basis (eigh_fold_view) skips the unfold + rank merge of folded problems
+    bool need_merged = true;
+    // 0 = the whole solve.  Staged (capi.hip: TChain -- the log-likelihood's shifted tridiagonal systems need the temporal side only
+    // as far as A / amax = Q T Q^T), same request every time:
+    //   1 = the tridiagonalisation (chain stream);
+    //   3 = the T factors of its reflector panels and the orthogonal factor Q itself (eigh_Q_view; T in EigArenaView::d / e) -- on
+    //       ANY stream behind stage 1: it reads the reflectors, which stages 2 and 4 leave alone;
+    //   2 = the divide & conquer of the tridiagonal matrix (chain stream, behind stage 1);
+    //   4 = the back-transformation (chain stream, behind stage 2 AND stage 3: it needs the T factors);
+    //   5 = stage 3 panel by panel beside a running stage 1 that publishes its progress, each block of columns followed by `x`.
+    // Staged solves need folded (prefolded or not), tridiagonalisation-path problems within the fused back-transformation's size
+    // (eigh_stageable).
+    int stage = 0;
+    bool progress = false;           // stage 1: the register tails publish their progress panel by panel (a stage 5 follows)
+    bool claim_psd = false;          // the caller vouches that its matrices are positive semi-definite (gpcsd_eigh_psd)
+    QPipeX x;                        // stage 5 only
+};
+void eigh_pair_device(gpcsd_ctx *c, const EighCall &r, hipStream_t s);
 bool eigh_stageable(const SymDev *sy, int n);
 // Q of class `tag` after stage 3: (n, n) row-major per replica, replicas n*n apart
 double *eigh_Q_view(gpcsd_ctx *c, const char *tag, int n, int count);

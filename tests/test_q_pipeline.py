@@ -201,3 +201,65 @@ def test_a_gate_that_gives_up_is_a_scheduling_miss_and_the_call_is_evaluated_aga
     finally:
         ctx.q_pipeline_stats(gate_ticks=20000000)
         ctx.q_pipeline(True)
+
+
+def test_interleaved_call_forms_replay_their_own_graphs():
+    """Every argument of a solve travels in its request, and the graph key is formed from the request: call forms interleaved on ONE
+    context -- fenced log-likelihood, fenced resident prediction, the queued pair, the gradient, eigh and eigh_psd of a caller's
+    matrix -- must each get their own graphs.  Round 1 runs eager, later rounds capture and replay; a key that forgot a field of a
+    request (progress words, the PSD claim, the stage, a replica count) would show up as one form replaying another's graph.
+    Halves of 66 / 65 rows, the smallest that stage (both above 64: one panel plus the remainder); 16 trials, the fewest at which the
+    prediction takes the tridiagonal form, so that stage 5 applies."""
+    import bench
+    from gpcsd_amd import _hip
+    nt, R = 131, 16
+    w = bench.workload("cfg2")
+    w["nt"] = nt
+    w["t"] = 0.5 * np.arange(float(nt))[:, None]
+    m = bench.build_model(w, np.zeros((w["nx"], nt, 1)))
+    lfp = bench.synth_data(w, m, R, seed=nt)
+    m.update_lfp(lfp, w["t"])
+    O_, geom, ohp, ohp0 = bench.oracle_setup(w, m)
+    ctx = m._sync_device()
+    ctx.decomposition_cache(False)
+    ctx.pair_share_s(False)
+    ctx.ll_tridiag(1)
+    z = w["x"]
+    hp, k1 = m._hparams(m.JITTER)
+    hp0, k0 = m._hparams(0.0)
+    ng = 1 + m.dim + 2 * len(m.temporal_cov_list) + 1
+    tt = w["t"][:, 0]
+    A = np.exp(-0.5 * ((tt[:, None] - tt[None, :]) / 9.0) ** 2)      # a fixed 131 x 131 Gram matrix: positive semi-definite
+    shape = (z.shape[0], nt, R)
+    rounds = []
+    try:
+        for _ in range(4):
+            n0 = ctx.q_pipeline()
+            r = {}
+            r["fenced_ll"] = ctx.loglik_parts(hp)
+            ctx.predict_resident(hp0, z, w["t"], _hip.PRED_CSD, want_lists=True)
+            r["fenced_pred"] = ctx.fetch("pred_out_csd", shape).copy()
+            ctx.loglik_predict_async(hp, hp0, z, w["t"], _hip.PRED_CSD, want_lists=True)
+            r["pair_ll"] = ctx.loglik_parts_wait()
+            r["pair_pred"] = ctx.fetch("pred_out_csd", shape).copy()
+            r["grad"] = ctx.loglik_grad(hp, ng)
+            r["eigh"] = ctx.eigh(A)
+            r["eigh_psd"] = ctx.eigh(A, psd=True)
+            r["piped"] = ctx.q_pipeline() - n0
+            rounds.append(r)
+    finally:
+        ctx.ll_tridiag(2)
+    first = rounds[0]
+    for k, r in enumerate(rounds):
+        assert r["piped"] >= 1, (k, r["piped"])                      # at least one pipelined chain per round
+        assert tuple(r["fenced_ll"]) == tuple(first["fenced_ll"]), k
+        assert np.array_equal(r["fenced_pred"], first["fenced_pred"]), k
+        assert tuple(r["pair_ll"]) == tuple(r["fenced_ll"]), k       # the pair: the bits of its fenced calls
+        assert np.array_equal(r["pair_pred"], r["fenced_pred"]), k
+        assert r["grad"][0] == first["grad"][0] and r["grad"][1] == first["grad"][1] and np.array_equal(r["grad"][2], first["grad"][2]), k
+        for form in ("eigh", "eigh_psd"):
+            assert np.array_equal(r[form][0], first[form][0]) and np.array_equal(r[form][1], first[form][1]), (k, form)
+    ll = -0.5 * R * first["fenced_ll"][0] - 0.5 * first["fenced_ll"][1]
+    ll_ref = O.loglik(geom, ohp, lfp)
+    print("interleaved forms: loglik vs oracle %.1e" % (abs(ll - ll_ref) / abs(ll_ref)))
+    assert abs(ll - ll_ref) <= 1e-9 * abs(ll_ref)
