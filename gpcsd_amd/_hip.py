@@ -128,6 +128,8 @@ SIGNATURES = {
     "gpcsd_whitened_quad": (_I, [_P, _DP, _I, _DP, _I, _DP, _DP, _I, _DP]),
     "gpcsd_debug_sytrd": (_I, [_P, _DP, _I, _DP, _DP, _DP, _DP]),
     "gpcsd_debug_stedc": (_I, [_P, _DP, _DP, _I, _DP, _DP]),
+    "gpcsd_debug_ll_tridiag": (_I, [_P, _DP, _DP, _I, _I, _I, _DP, _DP, _D, _I, _I, _DP, _DP, _D, _I, _I, _D, _I, _DP, _DP]),
+    "gpcsd_debug_tridiag_solve": (_I, [_P, _DP, _DP, _I, _I, _I, _DP, _DP, _D, _I, _I, _DP, _DP, _D, _I, _I, _D, _I, _DP]),
     "gpcsd_potrf": (_I, [_P, _DP, _I, _DP]),
     "gpcsd_logdet_chol": (_I, [_P, _DP, _I, _DP]),
     "gpcsd_trsm_lower": (_I, [_P, _DP, _I, _DP, _I, _DP]),
@@ -607,6 +609,44 @@ class Context:
         w, Z = np.empty(n), np.empty((n, n))
         self._check(self._lib.gpcsd_debug_stedc(self._h, _ptr(d), _ptr(e), n, _ptr(w), _ptr(Z)))
         return w, Z
+
+    @staticmethod
+    def _tri_operands(W, es, blocks):
+        W = _arr(W)
+        if W.ndim != 3:
+            raise ValueError("W must have shape (nx, R, nt)")
+        es = _arr(np.asarray(es, dtype=np.float64).reshape(-1), (W.shape[0],), "es")
+        args, keep = [], []
+        if len(blocks) != 2:
+            raise ValueError("two parity blocks (d, e, m, c0) are expected")
+        for d, e, m, c0 in blocks:
+            d, e = _arr(d).reshape(-1), _arr(e).reshape(-1)
+            if e.size != max(d.size - 1, 0):
+                raise ValueError("a block of %d columns needs %d off-diagonal entries, got %d" % (d.size, max(d.size - 1, 0), e.size))
+            keep += [d, e]
+            args += [_ptr(d) if d.size else None, _ptr(e) if e.size else None, float(m), int(d.size), int(c0)]
+        return W, es, args, keep
+
+    def debug_ll_tridiag(self, W, es, blocks, sig2, variant=0):
+        """The log-likelihood's shifted-tridiagonal kernel on its own.  W (nx, R, nt); es (nx,); blocks = two tuples (d, e, m, c0):
+        item (x, p) is A = es[x] m_p tridiag(d_p, e_p) + sig2 I on the columns [c0_p, c0_p + len(d_p)) of W[x].  variant 0: the
+        library's choice, 1: serial pivots, 2: pivot scan.  Returns (quad (nx, 2), logdet (nx, 2), sums (2,) = their totals)."""
+        W, es, args, keep = self._tri_operands(W, es, blocks)
+        nx, R, nt = W.shape
+        partials, sums = np.empty(4 * nx), np.empty(2)
+        self._check(self._lib.gpcsd_debug_ll_tridiag(self._h, _ptr(W), _ptr(es), nx, R, nt, *args, float(sig2), int(variant),
+                                                     _ptr(partials), _ptr(sums)))
+        return partials[:2 * nx].reshape(nx, 2), partials[2 * nx:].reshape(nx, 2), sums
+
+    def debug_tridiag_solve(self, W, es, blocks, sig2, trials_per_pass=0):
+        """The prediction's shifted-tridiagonal solve on its own (operands as debug_ll_tridiag): a copy of W whose block columns
+        hold A^-1 w.  trials_per_pass 0: the library's choice, 32 or 64."""
+        W, es, args, keep = self._tri_operands(W, es, blocks)
+        nx, R, nt = W.shape
+        B = np.empty_like(W)
+        self._check(self._lib.gpcsd_debug_tridiag_solve(self._h, _ptr(W), _ptr(es), nx, R, nt, *args, float(sig2),
+                                                        int(trials_per_pass), _ptr(B)))
+        return B
 
     def eig_D(self, Ks, Kt, sig2n):
         Ks, Kt = _arr(Ks), _arr(Kt)

@@ -265,6 +265,78 @@ extern "C" int gpcsd_debug_stedc(gpcsd_ctx *c, const double *d, const double *e,
     GP_API_END(c)
 }
 
+// diagnostics: the shifted-tridiagonal kernels of the basis U (x) Q on their own (gram.hip: k_ll_tridiag, k_tridiag_solve), host
+// arrays in and out.  W (nx, R, nt); es (nx); block p: diagonal d_p (np_p), off-diagonal e_p (np_p - 1), scale m_p, first column c0_p.
+struct DbgTriOperands {
+    const double *W, *es, *d[2], *e[2], *am[2], *sig;
+    int np[2], c0[2];
+};
+static DbgTriOperands dbg_tri_upload(gpcsd_ctx *c, const char *who, const double *W, const double *es, int nx, int R, int nt,
+                                     const double *d0, const double *e0, double m0, int np0, int c00, const double *d1,
+                                     const double *e1, double m1, int np1, int c01, double sig2) {
+    GP_REQUIRE(W && es && nx > 0 && R > 0 && nt > 0 && np0 >= 0 && np1 >= 0, -3, "%s: bad arguments", who);
+    GP_REQUIRE((np0 == 0 || d0) && (np1 == 0 || d1) && (np0 < 2 || e0) && (np1 < 2 || e1), -3, "%s: a block without its tridiagonal", who);
+    GP_REQUIRE(c00 >= 0 && c01 >= 0 && (long)c00 + np0 <= nt && (long)c01 + np1 <= nt, -3, "%s: a block leaves the rows of %d columns", who, nt);
+    DbgTriOperands o{};
+    o.W = c->upload<double>("dbg_tri_W", W, (size_t)nx * R * nt);
+    o.es = c->upload<double>("dbg_tri_es", es, nx);
+    const double *hd[2] = {d0, d1}, *he[2] = {e0, e1};
+    const int np[2] = {np0, np1}, c0[2] = {c00, c01};
+    for (int p = 0; p < 2; ++p) {
+        o.np[p] = np[p]; o.c0[p] = c0[p];
+        o.d[p] = c->upload<double>(p ? "dbg_tri_d1" : "dbg_tri_d0", hd[p], np[p]);
+        double *de = c->buf<double>(p ? "dbg_tri_e1" : "dbg_tri_e0", np[p]);       // np entries as in the arenas: the last is unused
+        GP_HIP(hipMemsetAsync(de, 0, std::max(np[p], 1) * sizeof(double), c->stream));
+        if (np[p] > 1) c->copy_in(de, he[p], (np[p] - 1) * sizeof(double), c->stream);
+        o.e[p] = de;
+    }
+    const double sc[3] = {m0, m1, sig2};
+    const double *dsc = c->upload<double>("dbg_tri_scal", sc, 3);
+    o.am[0] = dsc; o.am[1] = dsc + 1; o.sig = dsc + 2;
+    return o;
+}
+static int dbg_tri_idle(gpcsd_ctx *c) {                    // the launchers' scratch is the fused path's: start from an idle context
+    if (int rc = drain_async(c)) return rc;
+    GP_HIP(hipStreamSynchronize(c->stream2));
+    GP_HIP(hipStreamSynchronize(c->stream3));
+    GP_HIP(hipStreamSynchronize(c->stream4));
+    return 0;
+}
+
+extern "C" int gpcsd_debug_ll_tridiag(gpcsd_ctx *c, const double *W, const double *es, int nx, int R, int nt, const double *d0,
+                                      const double *e0, double m0, int np0, int c00, const double *d1, const double *e1, double m1,
+                                      int np1, int c01, double sig2, int variant, double *partials, double *sums) {
+    GP_API_BEGIN(c)
+    GP_REQUIRE(partials && sums && variant >= 0 && variant <= 2, -3, "debug_ll_tridiag: bad arguments");
+    if (int rc = dbg_tri_idle(c)) return rc;
+    const DbgTriOperands o = dbg_tri_upload(c, "debug_ll_tridiag", W, es, nx, R, nt, d0, e0, m0, np0, c00, d1, e1, m1, np1, c01, sig2);
+    double *out = c->buf<double>("dbg_tri_sums", 2);
+    k_ll_tridiag(c, o.W, o.es, o.d, o.e, o.am, o.sig, nx, R, nt, o.np, o.c0, out, out + 1, c->stream, nullptr, nullptr, 0, 0, variant);
+    double h[2];
+    c->download(h, out, sizeof(h));
+    c->download(partials, c->buf<double>("ll_tridiag_partials", (size_t)4 * nx), (size_t)4 * nx * sizeof(double));
+    c->sync();
+    sums[0] = h[1];                                        // (quadratic form first, as in the partials)
+    sums[1] = h[0];
+    return 0;
+    GP_API_END(c)
+}
+
+extern "C" int gpcsd_debug_tridiag_solve(gpcsd_ctx *c, const double *W, const double *es, int nx, int R, int nt, const double *d0,
+                                         const double *e0, double m0, int np0, int c00, const double *d1, const double *e1,
+                                         double m1, int np1, int c01, double sig2, int pass, double *B) {
+    GP_API_BEGIN(c)
+    GP_REQUIRE(B && (pass == 0 || pass == 32 || pass == 64), -3, "debug_tridiag_solve: bad arguments");
+    if (int rc = dbg_tri_idle(c)) return rc;
+    const DbgTriOperands o = dbg_tri_upload(c, "debug_tridiag_solve", W, es, nx, R, nt, d0, e0, m0, np0, c00, d1, e1, m1, np1, c01, sig2);
+    double *dB = const_cast<double *>(o.W);                // B starts as W and is solved in place, as in the prediction
+    k_tridiag_solve(c, dB, dB, o.es, o.d, o.e, o.am, o.sig, nx, R, nt, o.np, o.c0, c->stream, pass);
+    c->download(B, dB, (size_t)nx * R * nt * sizeof(double));
+    c->sync();
+    return 0;
+    GP_API_END(c)
+}
+
 extern "C" int gpcsd_eig_D(gpcsd_ctx *c, const double *Ks, int nx, const double *Kt, int nt, const double *sig2n, int n_sig,
                            double *Qs, double *Qt, double *Dvec) {
     GP_API_BEGIN(c)

@@ -454,11 +454,22 @@ __global__ __launch_bounds__(64 * LT_WAVES) void ll_tridiag_kernel(LlTridiagArgs
 // theta_{k-1} of leading principal minors, (theta_k, theta_{k-1})^T = M_k (theta_{k-1}, theta_{k-2})^T with M_k = [[a_k,
 // -b_{k-1}^2], [1, 0]]: lane j multiplies the M_k of its LS_CPL consecutive columns, a wave scan (six shuffle steps, every
 // product renormalised by a power of two: positive definite, all minors positive) gives each lane the product of everything
-// in front of it, and a second walk over its own columns the pivots themselves.  One step of the exact recurrence from the
-// neighbour's pivot (D_k = a_k - b_{k-1}^2 / D_{k-1}, all columns at once) then removes what the re-associated products
-// lost: a relative error delta in D_{k-1} reaches D_k multiplied by b^2 / (D_{k-1} D_k) < 1.  Multipliers and reciprocal
-// pivots go to LDS as pairs; a column step of the sweep is ONE dependent FMA (z) plus one on a rotating accumulator (q),
-// coefficients by LDS broadcast reads a chunk ahead of their use.
+// in front of it, and a second walk over its own columns the pivots themselves.
+// What the products lose: theta_j = det(A[i..j]) theta_{i-1} - b_{i-1}^2 det(A[i+1..j]) theta_{i-2} is a difference of two terms
+// that can both be ~ min(i, j - i) times the result (the (2, -1) Toeplitz matrix: minors k + 1), so the scan's pivots are off by
+// 1e2 .. 1e4 u where the sequential recurrence loses a few u.  One step of the exact recurrence from the neighbour's pivot (D_k =
+// a_k - b_{k-1}^2 / D_{k-1}, all columns at once) does NOT repair that: a relative error delta in D_{k-1} reaches D_k multiplied
+// by g_k = b_{k-1}^2 / (D_{k-1} D_k) = a_k / D_k - 1, which is below 1 only while D_k > a_k / 2 -- about 1 for the Toeplitz
+// matrix, of the order of the condition number when sig2 << lam m d_k.  (Measured on the MI355X against a 50-digit reference,
+// tests/test_tridiag_kernels.py: with that step alone the quadratic form was up to 988 times further off than the plain
+// sequential float64 recurrence, the solve below -- the same scan without the step -- up to 1430 times)
+// So the scan's pivots D0 get one Newton step of the whole recurrence first: with D_k = D0_k (1 + eta_k), to first order
+// eta_k = g_k eta_{k-1} - rho_k, rho_k = 1 - (a_k - b_{k-1}^2 / D0_{k-1}) / D0_k the relative residual (one FMA: exact up to
+// the rounding of its small result).  That is an affine recurrence: a second wave scan, of pairs (G, H): eta -> G eta + H,
+// in which nothing cancels (g >= 0).  The exact step from the corrected neighbour follows: its own rounding is the sequential
+// recurrence's, what it inherits is second order in the scan's error.
+// Multipliers and reciprocal pivots go to LDS as pairs; a column step of the sweep is ONE dependent FMA (z) plus one on a
+// rotating accumulator (q), coefficients by LDS broadcast reads a chunk ahead of their use.
 constexpr int LS_CPL = 4;                                           // columns per lane in the scan: blocks of up to 256 columns
 typedef double dbl2_t __attribute__((ext_vector_type(2)));
 __global__ __launch_bounds__(64 * LT_WAVES) void ll_tridiag_scan_kernel(LlTridiagArgs g) {
@@ -550,7 +561,41 @@ __global__ __launch_bounds__(64 * LT_WAVES) void ll_tridiag_scan_kernel(LlTridia
         for (int cc = 0; cc < LS_CPL; ++cc) pexc[wid][lane * LS_CPL + cc + 1] = pv[cc];
         if (lane == 0) pexc[wid][0] = 0.0;
         __builtin_amdgcn_wave_barrier();
-        // one step of the exact recurrence, every column from its left neighbour's reciprocal pivot
+        // one Newton step on all pivots at once (see above): eta_k = g_k eta_{k-1} - rho_k, the maps eta -> G eta + H of the
+        // lanes composed by a second wave scan (g >= 0: nothing cancels in it, and a product of g is a sensitivity of one pivot
+        // to another, bounded by the condition: no renormalisation)
+        {
+            double gk[LS_CPL], rk[LS_CPL], G = 1.0, H = 0.0;
+#pragma unroll
+            for (int cc = 0; cc < LS_CPL; ++cc) {
+                const double pl = pexc[wid][lane * LS_CPL + cc];       // 1 / D_{k-1} of the scan (0 in front of the block)
+                const double sk = fma(-b2[cc], pl, a[cc]);             // what the recurrence makes of it
+                rk[cc] = fma(-pv[cc], sk, 1.0);
+                gk[cc] = b2[cc] * pl * pv[cc];
+                H = fma(gk[cc], H, -rk[cc]);
+                G *= gk[cc];
+            }
+#pragma unroll
+            for (int dlt = 1; dlt < 64; dlt <<= 1) {
+                const double Ge = __shfl_up(G, dlt), He = __shfl_up(H, dlt);
+                if (lane >= dlt) {
+                    H = fma(G, He, H);
+                    G *= Ge;
+                }
+            }
+            double eta = __shfl_up(H, 1);
+            if (lane == 0) eta = 0.0;
+#pragma unroll
+            for (int cc = 0; cc < LS_CPL; ++cc) {
+                eta = fma(gk[cc], eta, -rk[cc]);
+                pv[cc] = fma(-pv[cc], eta, pv[cc]);                    // 1 / (D_k (1 + eta_k)) to first order
+            }
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int cc = 0; cc < LS_CPL; ++cc) pexc[wid][lane * LS_CPL + cc + 1] = pv[cc];
+            __builtin_amdgcn_wave_barrier();
+        }
+        // one step of the exact recurrence, every column from its left neighbour's corrected reciprocal pivot
         double dk[LS_CPL], lg = 0.0;
 #pragma unroll
         for (int cc = 0; cc < LS_CPL; ++cc) {
@@ -647,7 +692,7 @@ void ll_tridiag_reduce_launch(gpcsd_ctx *c, const double *partials, int nitems, 
 bool k_ll_tridiag(gpcsd_ctx *c, const double *W, const double *es, const double *const d[2], const double *const e[2],
                   const double *const amax[2], const double *sig, int nx, int R, int nt, const int np[2], const int c0[2],
                   double *out_sumlog, double *out_quad, hipStream_t s, double *host_slot, const double *status_src, int status_at,
-                  int status_doubles) {
+                  int status_doubles, int variant) {
     LlTridiagArgs g{};
     g.W = W; g.es = es; g.sig = sig; g.nx = nx; g.R = R; g.nt = nt;
     for (int p = 0; p < 2; ++p) {
@@ -656,7 +701,10 @@ bool k_ll_tridiag(gpcsd_ctx *c, const double *W, const double *es, const double 
     const int nitems = 2 * nx;
     g.partials = c->buf<double>("ll_tridiag_partials", (size_t)2 * nitems);
     ProfScope ps(c, "ll_tridiag", 0.0, s);
-    static const bool serial = getenv("GPCSD_LL_PIVOT_SCAN") && getenv("GPCSD_LL_PIVOT_SCAN")[0] == '0';
+    static const bool serial_env = getenv("GPCSD_LL_PIVOT_SCAN") && getenv("GPCSD_LL_PIVOT_SCAN")[0] == '0';
+    const bool serial = variant ? variant == 1 : serial_env;       // (variant: the caller's choice instead of the environment's)
+    GP_REQUIRE(variant != 2 || std::max(np[0], np[1]) <= 64 * LS_CPL, -3, "ll_tridiag: the scan kernel takes blocks of at most %d columns",
+               64 * LS_CPL);
     if (!serial && std::max(np[0], np[1]) <= 64 * LS_CPL)
         hipLaunchKernelGGL(ll_tridiag_scan_kernel, dim3(ceil_div(nitems, LT_WAVES)), dim3(64 * LT_WAVES), 0, s, g);
     else
@@ -788,8 +836,36 @@ __global__ __launch_bounds__(256, P == 32 ? 2 : 1) void tridiag_solve_kernel(Tri
                 }
             }
             // first column of the prefix product = (theta_k, theta_{k-1}) up to a common factor
-            const double pk = m10 / m00;                             // 1 / D_k
+            double pk = m10 / m00;                                   // 1 / D_k of the scan
+            // The re-associated products cancel (a segment's minors against the minors in front of it): these pivots are off by
+            // 1e2 .. 1e4 u where the sequential recurrence loses a few u.  One Newton step on all of them at once, as in
+            // ll_tridiag_scan_kernel: with D_k (1 + eta_k) the exact pivots, eta_k = g_k eta_{k-1} - rho_k to first order, rho_k =
+            // 1 - (a_k - b^2 / D_{k-1}) / D_k the relative residual of the recurrence and g_k = b^2 / (D_{k-1} D_k) >= 0 -- an
+            // affine scan, eight doubling steps on pairs (G, H): eta -> G eta + H; then one step of the exact recurrence.
+            const double b2 = bkm * bkm;
+            buf[k] = pk;
+            __syncthreads();
+            const double pl = k >= 1 ? buf[k - 1] : 0.0;
+            const double rho = fma(-pk, fma(-b2, pl, ak), 1.0);
+            double G = b2 * pl * pk, H = -rho;
+            __syncthreads();
+#pragma unroll 1
+            for (int dlt = 1; dlt < 256; dlt <<= 1, buf = (buf == scan) ? scan + 1024 : scan) {
+                buf[2 * k + 0] = G; buf[2 * k + 1] = H;
+                __syncthreads();
+                if (k >= dlt) {
+                    const double Ge = buf[2 * (k - dlt) + 0], He = buf[2 * (k - dlt) + 1];
+                    H = fma(G, He, H);
+                    G *= Ge;
+                }
+            }
+            pk = fma(-pk, H, pk);                                    // 1 / (D_k (1 + eta_k)) to first order
+            buf[k] = pk;
+            __syncthreads();
+            const double pl1 = k >= 1 ? buf[k - 1] : 0.0;
+            pk = 1.0 / fma(-b2, pl1, ak);                            // the exact recurrence from the corrected left neighbour
             pinv[k] = real ? pk : 1.0;
+            __syncthreads();
             buf[k] = pk;
             __syncthreads();
             lmul[k] = (k >= 1 && real) ? bkm * buf[k - 1] : 0.0;     // l_k = b_{k-1} / D_{k-1}; zero through the padding columns
@@ -895,7 +971,7 @@ int k_tridiag_solve_pass(int npmax, int R) {
 
 void k_tridiag_solve(gpcsd_ctx *c, const double *W, double *B, const double *es, const double *const d[2], const double *const e[2],
                      const double *const amax[2], const double *sig, int nx, int R, int nt, const int np[2], const int c0[2],
-                     hipStream_t s) {
+                     hipStream_t s, int pass) {
     TriSolveArgs g{};
     g.W = W; g.B = B; g.es = es; g.sig = sig; g.nx = nx; g.R = R; g.nt = nt;
     for (int p = 0; p < 2; ++p) {
@@ -903,6 +979,7 @@ void k_tridiag_solve(gpcsd_ctx *c, const double *W, double *B, const double *es,
     }
     const int npmax = std::max(np[0], np[1]);
     GP_REQUIRE(k_tridiag_solve_pass(npmax, R) > 0, -3, "tridiag_solve: temporal blocks of %d columns do not fit the solve kernel", npmax);
+    GP_REQUIRE(pass == 0 || pass == 32 || pass == 64, -3, "tridiag_solve: %d trials per pass (0 = by size, 32 or 64)", pass);
     g.npad = tridiag_solve_npad(npmax);
     // Trials per pass: 64 (a lane each: one pass for up to 64 trials, 131 KB of LDS and 336 registers per lane: nothing else lives
     // on a CU beside such a workgroup) or 32 (two passes for 50 trials; 66 KB, 193 registers: two per CU, and other streams'
@@ -912,7 +989,7 @@ void k_tridiag_solve(gpcsd_ctx *c, const double *W, double *B, const double *es,
     // announcements the chains are not there to be disturbed and the narrow form's second pass costs 2.4 %: 0.811 against 0.792).
     // Up to 32 trials the narrow form is one pass as well and always taken.  GPCSD_TS_P=32|64 forces one (A/B).
     static const int forced = getenv("GPCSD_TS_P") ? (atoi(getenv("GPCSD_TS_P")) == 32 ? 32 : 64) : 0;
-    const int P = forced ? forced : (R <= 32 || c->solve_pass == 32) ? 32 : TS_P_DEFAULT;
+    const int P = pass ? pass : forced ? forced : (R <= 32 || c->solve_pass == 32) ? 32 : TS_P_DEFAULT;     // (pass: the caller's choice first)
     const size_t lds = tridiag_solve_lds(npmax, P);
     static size_t attr_dev[64][2] = {};            // (per device: the attribute belongs to the device's copy of the kernel)
     size_t *attr = attr_dev[c->device & 63];

@@ -134,17 +134,20 @@ void k_se_axis_tab(gpcsd_ctx *c, const double *a, int n, int axis, const HpDev *
 // W = U^T Y Q ([x'][r][t~], rows of nt) of w^T (.)^-1 w by one forward recurrence each.  No temporal eigenvectors.
 // host_slot (pinned, device-accessible) != null: the final sums' launch also writes {sum log D, quadratic form} to host_slot[0..1]
 // and the status_doubles doubles at status_src to host_slot + status_at -- returns true when it did (the caller then skips its copy)
+// variant: 0 = the launcher's choice (the scan kernel for blocks of at most 256 columns unless GPCSD_LL_PIVOT_SCAN=0), 1 = the
+// serial-pivot kernel, 2 = the scan kernel (-3 for a wider block); the per-item partials stay in the ctx buffer "ll_tridiag_partials"
 bool k_ll_tridiag(gpcsd_ctx *c, const double *W, const double *es, const double *const d[2], const double *const e[2],
                   const double *const amax[2], const double *sig, int nx, int R, int nt, const int np[2], const int c0[2],
                   double *out_sumlog, double *out_quad, hipStream_t s, double *host_slot = nullptr, const double *status_src = nullptr,
-                  int status_at = 0, int status_doubles = 0);
+                  int status_at = 0, int status_doubles = 0, int variant = 0);
 // The same systems solved: B[x'][r][p block] = (es[x'] amax_p T_p + sig2 I)^-1 W[x'][r][p block] (B may be W).  The posterior mean
 // in the basis U (x) Q -- what (W V) / D is in the basis U (x) V -- without the temporal eigenvectors.
 // k_tridiag_solve_pass: trials per pass of the kernel for column blocks of up to npmax (its z lives in LDS); 0 = unsupported.
+// pass: 0 = the launcher's choice (GPCSD_TS_P, the trial count, gpcsd_ctx::solve_pass), 32 or 64 = that form.
 int k_tridiag_solve_pass(int npmax, int R);
 void k_tridiag_solve(gpcsd_ctx *c, const double *W, double *B, const double *es, const double *const d[2], const double *const e[2],
                      const double *const amax[2], const double *sig, int nx, int R, int nt, const int np[2], const int c0[2],
-                     hipStream_t s);
+                     hipStream_t s, int pass = 0);
 void k_add_diag(gpcsd_ctx *c, double *A, int n, double v, hipStream_t s, const HpDev *tab = nullptr, int B = 1, long s_out = 0);
 void k_shift_copy(gpcsd_ctx *c, const double *src, double *dst, int n, double v, hipStream_t s);     // dst = src + v
 void k_sum_partials(gpcsd_ctx *c, double *out, const double *P, long n, int parts, hipStream_t s);

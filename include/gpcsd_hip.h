@@ -171,6 +171,21 @@ int gpcsd_eigh_batch(gpcsd_ctx *ctx, const double *A, int n, int count, double *
 int gpcsd_debug_sytrd(gpcsd_ctx *ctx, const double *A, int n, double *d, double *e, double *V, double *tau);
 /* divide & conquer eigen-decomposition of tridiag(d (n), e (n-1)): w ascending, Z (n,n) eigenvectors in columns */
 int gpcsd_debug_stedc(gpcsd_ctx *ctx, const double *d, const double *e, int n, double *w, double *Z);
+/* Diagnostics for the shifted-tridiagonal kernels of the default step (no reference counterpart): item (x', p) is the system
+ * A = es[x'] m_p T_p + sig2 I with T_p = tridiag(d_p (np_p), e_p (np_p - 1)); W (nx, R, nt) holds its right-hand sides in the
+ * columns [c0_p, c0_p + np_p) of the rows [x'][r].  variant: 0 the library's choice, 1 serial pivots, 2 pivot scan (-3 for a
+ * block of more than 256 columns).  partials (4 nx): w^T A^-1 w summed over r per item (2 x' + p), then log det A per item;
+ * sums (2): the totals of the two halves as the step forms them (quadratic forms, log-determinants). */
+int gpcsd_debug_ll_tridiag(gpcsd_ctx *ctx, const double *W, const double *es, int nx, int R, int nt,
+                           const double *d0, const double *e0, double m0, int np0, int c00,
+                           const double *d1, const double *e1, double m1, int np1, int c01,
+                           double sig2, int variant, double *partials, double *sums);
+/* the same systems solved: B (nx, R, nt) = W with the blocks' columns replaced by A^-1 w, every other column untouched.
+ * pass: trials per pass of the kernel, 0 the library's choice, 32 or 64.  -3 for R < 16 or a block of more than 256 columns. */
+int gpcsd_debug_tridiag_solve(gpcsd_ctx *ctx, const double *W, const double *es, int nx, int R, int nt,
+                              const double *d0, const double *e0, double m0, int np0, int c00,
+                              const double *d1, const double *e1, double m1, int np1, int c01,
+                              double sig2, int pass, double *B);
 /* comp_eig_D(Ks, Kt, sig2n)            utility_functions.py:44-64 ; Dvec has nx*nt entries */
 int gpcsd_eig_D(gpcsd_ctx *ctx, const double *Ks, int nx, const double *Kt, int nt,
                 const double *sig2n, int n_sig, double *Qs, double *Qt, double *Dvec);
