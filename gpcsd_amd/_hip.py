@@ -146,6 +146,8 @@ SIGNATURES = {
     "gpcsd_loglik_grad_batch": (_I, [_P, ctypes.POINTER(HParams), _I, _DP, _DP, _I, ctypes.POINTER(_I)]),
     "gpcsd_predict": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _DP, _DP, _DP, _DP]),
     "gpcsd_predict_resident": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _I]),
+    "gpcsd_predict_at": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _DP, _DP, _DP, _DP]),
+    "gpcsd_predict_at_resident": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _I]),
     "gpcsd_fetch": (_I, [_P, ctypes.c_char_p, _DP, _L]),
     "gpcsd_device_buffer": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
     "gpcsd_sample_prior": (_I, [_P, ctypes.POINTER(HParams), _I, _DP, _I, _DP]),
@@ -793,8 +795,9 @@ class Context:
                                                       st.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return out[:, 0].copy(), out[:, 1].copy(), g, st
 
-    def predict(self, hp, z, tstar, type_code, shape, want_lists=True):
-        """shape = (nz, ntstar, ntrials).  Returns dict of arrays for the requested type."""
+    def predict(self, hp, z, tstar, type_code, shape, want_lists=True, at=False):
+        """shape = (nz, ntstar, ntrials).  Returns dict of arrays for the requested type.  at=True: gpcsd_predict_at (any ntstar,
+        the training axis of the cross Grams contracted) instead of gpcsd_predict."""
         z = _arr(z)
         tstar = _arr(tstar).reshape(-1)
         nz, ntstar, R = shape
@@ -808,19 +811,21 @@ class Context:
             else:
                 bufs[name] = None
                 bufs[name + "_list"] = None
-        self._check(self._lib.gpcsd_predict(self._h, ctypes.byref(hp), _ptr(z), nz, _ptr(tstar), tstar.size, int(type_code),
-                                            _ptr(bufs["csd_list"]), _ptr(bufs["csd"]), _ptr(bufs["lfp_list"]), _ptr(bufs["lfp"])))
+        fn = self._lib.gpcsd_predict_at if at else self._lib.gpcsd_predict
+        self._check(fn(self._h, ctypes.byref(hp), _ptr(z), nz, _ptr(tstar), tstar.size, int(type_code),
+                       _ptr(bufs["csd_list"]), _ptr(bufs["csd"]), _ptr(bufs["lfp_list"]), _ptr(bufs["lfp"])))
         for k, v in bufs.items():
             if v is not None:
                 res[k] = v
         return res
 
-    def predict_resident(self, hp, z, tstar, type_code, want_lists=True):
-        """Compute the posterior mean into device buffers only (no PCIe traffic); read back with fetch()."""
+    def predict_resident(self, hp, z, tstar, type_code, want_lists=True, at=False):
+        """Compute the posterior mean into device buffers only (no PCIe traffic); read back with fetch().  at=True:
+        gpcsd_predict_at_resident."""
         z = _arr(z)
         tstar = _arr(tstar).reshape(-1)
-        self._check(self._lib.gpcsd_predict_resident(self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size,
-                                                     int(type_code), int(bool(want_lists))))
+        fn = self._lib.gpcsd_predict_at_resident if at else self._lib.gpcsd_predict_resident
+        self._check(fn(self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size, int(type_code), int(bool(want_lists))))
 
     def fetch(self, name, shape):
         out = pinned_pool.empty(shape)

@@ -606,6 +606,63 @@ static bool pred_unfold_chunked(gpcsd_ctx *c, PredUnfoldDesc pu, int which0, int
     return true;
 }
 
+// What the full-size (unfolded) predictions share up to the last two products: W = Qs^T Y, the cross-covariances with
+// M1 = Kc^T Qs per requested output and the (ntstar, nt) temporal cross Grams queued beside the temporal eigensolver, then
+// Bm = (W Qt) / D.
+//   invy = (Qs (x) Qt) vec(Bm) (gpcsd1d.py:262-265) is never formed: the cross-covariance contraction
+//   out_c = Kc^T Qs Bm Qt^T Kt*_c  is re-associated as  (Kc^T Qs) Bm (Qt^T Kt*_c),
+// i.e. two small (n^3) products M1, Pc and two flat GEMMs, instead of back-projecting to the original bases first
+// (saves 2 nx^2 nt + 2 nx nt^2 flops per trial; identical up to rounding).
+struct PredFullFront {
+    double *Bm, *M1, *Kts;       // (nx, R, nt); (2, nz, nx): CSD, LFP; (C, ntstar, nt) = cov_c.compute_Kt(tstar)
+};
+static PredFullFront predict_full_front(gpcsd_ctx *c, const gpcsd_hparams *hp, EigState &e, const double *z, int nz, const double *tstar,
+                                        int ntstar, int type) {
+    const Geo g = resident_geo(c);
+    const int nx = c->nx, nt = c->nt, R = c->ntrials, C = hp->n_temporal;
+    const long RT = (long)R * nt;
+    hipStream_t s = c->stream;
+    double *W = c->buf<double>("proj_W", (size_t)nx * RT);
+    PredFullFront f;
+    f.Bm = c->buf<double>("pred_B", (size_t)nx * RT);
+    GemmDesc g1;                          // W = Qs^T Y
+    g1.M = nx; g1.N = (int)RT; g1.K = nx;
+    g1.A = e.Qs; g1.lda = nx; g1.transA = true;
+    g1.B = c->d_lfp; g1.ldb = RT; g1.C = W; g1.ldc = RT;
+    g1.prof_name = "gemm_proj_spatial";
+    gemm_f64(c, g1, s);
+    double *dz = c->upload_cached<double>("pred_z", z, (size_t)nz * g.dim);
+    double *dts = c->upload_cached<double>("pred_tstar", tstar, ntstar);
+    const double *t = (const double *)c->bufs["time_t"].p;
+    double *Kc = c->buf<double>("pred_Kcross", (size_t)nx * nz);
+    f.Kts = c->buf<double>("pred_Ktstar", (size_t)C * ntstar * nt);
+    f.M1 = c->buf<double>("pred_M1", (size_t)2 * nz * nx);
+    // Everything that needs only Qs is queued before the join, i.e. it runs beside the temporal eigensolver:
+    // cross-covariances Kc, M1 = Kc^T Qs for the requested outputs, and the prediction-time temporal Grams.
+    for (int which = 1; which <= 2; ++which) {
+        if (!(type & which)) continue;
+        if (which == 1) build_kphig(c, g, hp->R, hp->eps, hp->ell_s, dz, nz, Kc, s);        // gpcsd1d.py:273
+        else build_kphi(c, g, hp->R, hp->eps, hp->ell_s, dz, nz, 0.0, Kc, s);               // gpcsd1d.py:275
+        GemmDesc gm;                      // M1[z][x'] = sum_x Kc[x][z] Qs[x][x']
+        gm.M = nz; gm.N = nx; gm.K = nx;
+        gm.A = Kc; gm.lda = nz; gm.transA = true; gm.B = e.Qs; gm.ldb = nx; gm.C = f.M1 + (size_t)(which - 1) * nz * nx; gm.ldc = nx;
+        gm.prof_name = "gemm_pred_M1";
+        gemm_f64(c, gm, s);
+    }
+    GP_HIP(hipEventRecord(c->ev_m1, s));          // (a later paired call rewrites the cross-covariances on stream5)
+    c->m1_read_queued = true;
+    for (int cc = 0; cc < C; ++cc)
+        temporal_cross_gram(c, hp, cc, dts, ntstar, t, nt, f.Kts + (size_t)cc * ntstar * nt, s);
+    join_temporal(c, e, nullptr, false);      // predict never reads sum(log D)
+    GemmDesc g2;                          // Bm = (W Qt) / D
+    g2.M = nx * R; g2.N = nt; g2.K = nt;
+    g2.A = W; g2.lda = nt; g2.B = e.Qt; g2.ldb = nt; g2.C = f.Bm; g2.ldc = nt;
+    g2.epi = EPI_DIV_D; g2.D = e.Dinv; g2.rdiv = R; g2.ldd = nt;
+    g2.prof_name = "gemm_pred_temporal_div";
+    gemm_f64(c, g2, s);
+    return f;
+}
+
 // Posterior mean into ctx-owned device buffers, already in the reference's output layout (z, t, trial):
 //   pred_out_csd / pred_out_lfp            (nz, ntstar, R)
 //   pred_out_csd_list / pred_out_lfp_list  (C, nz, ntstar, R)     when want_lists
@@ -646,58 +703,17 @@ static int predict_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, 
         }
     }
     EigState e = front_half(c, hp, 0.0);           // no jitter in predict (gpcsd1d.py:258)
-    const Geo g = resident_geo(c);
     const int nx = c->nx, nt = c->nt, R = c->ntrials, C = hp->n_temporal;
     const long RT = (long)R * nt;
     hipStream_t s = c->stream;
-    double *W = c->buf<double>("proj_W", (size_t)nx * RT);
-    double *Bm = c->buf<double>("pred_B", (size_t)nx * RT);
-    GemmDesc g1;                          // W = Qs^T Y
-    g1.M = nx; g1.N = (int)RT; g1.K = nx;
-    g1.A = e.Qs; g1.lda = nx; g1.transA = true;
-    g1.B = c->d_lfp; g1.ldb = RT; g1.C = W; g1.ldc = RT;
-    g1.prof_name = "gemm_proj_spatial";
-    gemm_f64(c, g1, s);
-    // invy = (Qs (x) Qt) vec(Bm) (gpcsd1d.py:262-265) is never formed: the cross-covariance contraction
-    //   out_c = Kc^T Qs Bm Qt^T Kt*_c  is re-associated as  (Kc^T Qs) Bm (Qt^T Kt*_c),
-    // i.e. two small (n^3) products M1, Pc and two flat GEMMs, instead of back-projecting to the original bases first
-    // (saves 2 nx^2 nt + 2 nx nt^2 flops per trial; identical up to rounding).
-    double *dz = c->upload_cached<double>("pred_z", z, (size_t)nz * g.dim);
-    double *dts = c->upload_cached<double>("pred_tstar", tstar, ntstar);
-    const double *t = (const double *)c->bufs["time_t"].p;
-    double *Kc = c->buf<double>("pred_Kcross", (size_t)nx * nz);
+    // Ktstar_c = cov_c.compute_Kt(tstar): (ntstar, nt); its FIRST axis is contracted with the training
+    // time index (reference quirk when tstar != t)      gpcsd1d.py:277-279
+    const PredFullFront f = predict_full_front(c, hp, e, z, nz, tstar, ntstar, type);
+    double *const Bm = f.Bm, *const M1 = f.M1, *const Kts = f.Kts;
     double *S = c->buf<double>("pred_S", (size_t)nz * RT);
     double *comp = c->buf<double>("pred_comp", (size_t)C * nz * RT);
-    double *Kts = c->buf<double>("pred_Ktstar", (size_t)C * ntstar * nt);
-    double *M1 = c->buf<double>("pred_M1", (size_t)2 * nz * nx);
     double *Pc = c->buf<double>("pred_Pc", (size_t)C * nt * nt);
     const size_t out_elems = (size_t)nz * RT;
-    // Everything that needs only Qs is queued before the join, i.e. it runs beside the temporal eigensolver:
-    // cross-covariances Kc, M1 = Kc^T Qs for the requested outputs, and the prediction-time temporal Grams.
-    for (int which = 1; which <= 2; ++which) {
-        if (!(type & which)) continue;
-        if (which == 1) build_kphig(c, g, hp->R, hp->eps, hp->ell_s, dz, nz, Kc, s);        // gpcsd1d.py:273
-        else build_kphi(c, g, hp->R, hp->eps, hp->ell_s, dz, nz, 0.0, Kc, s);               // gpcsd1d.py:275
-        GemmDesc gm;                      // M1[z][x'] = sum_x Kc[x][z] Qs[x][x']
-        gm.M = nz; gm.N = nx; gm.K = nx;
-        gm.A = Kc; gm.lda = nz; gm.transA = true; gm.B = e.Qs; gm.ldb = nx; gm.C = M1 + (size_t)(which - 1) * nz * nx; gm.ldc = nx;
-        gm.prof_name = "gemm_pred_M1";
-        gemm_f64(c, gm, s);
-    }
-    GP_HIP(hipEventRecord(c->ev_m1, s));          // (a later paired call rewrites the cross-covariances on stream5)
-    c->m1_read_queued = true;
-    for (int cc = 0; cc < C; ++cc) {
-        // Ktstar_c = cov_c.compute_Kt(tstar): (ntstar, nt); its FIRST axis is contracted with the training
-        // time index (reference quirk when tstar != t)      gpcsd1d.py:277-279
-        temporal_cross_gram(c, hp, cc, dts, ntstar, t, nt, Kts + (size_t)cc * ntstar * nt, s);
-    }
-    join_temporal(c, e, nullptr, false);      // predict never reads sum(log D)
-    GemmDesc g2;                          // Bm = (W Qt) / D
-    g2.M = nx * R; g2.N = nt; g2.K = nt;
-    g2.A = W; g2.lda = nt; g2.B = e.Qt; g2.ldb = nt; g2.C = Bm; g2.ldc = nt;
-    g2.epi = EPI_DIV_D; g2.D = e.Dinv; g2.rdiv = R; g2.ldd = nt;
-    g2.prof_name = "gemm_pred_temporal_div";
-    gemm_f64(c, g2, s);
     for (int which = 1; which <= 2; ++which) {
         if (!(type & which)) continue;
         double *o_sum = c->buf<double>(which == 1 ? "pred_out_csd" : "pred_out_lfp", out_elems);
@@ -1177,6 +1193,88 @@ extern "C" int gpcsd_predict(gpcsd_ctx *c, const gpcsd_hparams *hp, const double
     c->sync();
     for (hipEvent_t ev : c->pred_sink_events) c->event_pool.push_back(ev);
     c->pred_sink_events.clear();
+    return rc;
+    GP_API_END(c)
+}
+
+// Posterior mean at ARBITRARY prediction times (gpcsd_predict_at; no reference counterpart): as the full-size path of predict_impl
+// up to S = (Kc^T Qs) Bm, then the TRAINING axis of the cross Grams is contracted,
+//   P_c[i'][j] = sum_i Qt[i][i'] k_c(t*_j, t_i),      out_c[z][j][r] = sum_i' S[(z, r)][i'] P_c[i'][j],
+// and the last product writes the output layout itself (gemm_pred_at).  Both sides unfolded: a window of t has no mirror symmetry.
+// Outputs: the buffers of predict_impl, (nz, ntstar, R) / (C, nz, ntstar, R).
+static int predict_at_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar,
+                           int type, bool want_lists) {
+    GP_REQUIRE(z && tstar && nz > 0 && ntstar > 0, -3, "predict_at: bad arguments");
+    GP_REQUIRE(type >= 1 && type <= 3, -3, "predict_at: type must be CSD(1), LFP(2) or BOTH(3)");
+    GP_REQUIRE(hp != nullptr, -3, "null hparams");
+    GP_REQUIRE(c->d_lfp != nullptr, -4, "lfp not set (call gpcsd_set_lfp)");
+    // (checked before tstar is read: one row of an output, and of the concatenated P_c, is a flat GEMM operand row)
+    GP_REQUIRE((long)c->ntrials * ntstar < GPCSD_MAX_GEMM_LD_KMAJOR && (long)std::max(hp->n_temporal, 1) * ntstar < GPCSD_MAX_GEMM_LD_KMAJOR &&
+                   (long)nz * c->ntrials < (1L << 31),
+               GPCSD_ERR_CAPACITY, "predict_at: ntrials * ntstar = %ld (or n_temporal * ntstar, or nz * ntrials) exceeds the capacity of "
+               "one output row (%ld doubles; GPCSD_MAX_GEMM_LD_KMAJOR)", (long)c->ntrials * ntstar, (long)GPCSD_MAX_GEMM_LD_KMAJOR);
+    EigState e = front_half(c, hp, 0.0);           // no jitter, as predict (gpcsd1d.py:258)
+    const int nx = c->nx, nt = c->nt, R = c->ntrials, C = hp->n_temporal;
+    const long RT = (long)R * nt;
+    hipStream_t s = c->stream;
+    const PredFullFront f = predict_full_front(c, hp, e, z, nz, tstar, ntstar, type);
+    double *const Bm = f.Bm, *const M1 = f.M1, *const Kts = f.Kts;
+    double *S = c->buf<double>("pred_S", (size_t)nz * RT);
+    double *Pc = c->buf<double>("pred_Pc", (size_t)C * nt * ntstar);
+    const size_t out_elems = (size_t)nz * ntstar * R;
+    for (int cc = 0; cc < C; ++cc) {
+        GemmDesc gp;                      // Pcat[i'][cc*ntstar + j] = sum_i Qt[i][i'] Ktstar_cc[j][i]: the TRAINING axis contracted
+        gp.M = nt; gp.N = ntstar; gp.K = nt;
+        gp.A = e.Qt; gp.lda = nt; gp.transA = true; gp.B = Kts + (size_t)cc * ntstar * nt; gp.ldb = nt; gp.transB = true;
+        gp.C = Pc + (size_t)cc * ntstar; gp.ldc = (long)C * ntstar;
+        gp.prof_name = "gemm_pred_Pc";
+        gemm_f64(c, gp, s);
+    }
+    for (int which = 1; which <= 2; ++which) {
+        if (!(type & which)) continue;
+        double *o_sum = c->buf<double>(which == 1 ? "pred_out_csd" : "pred_out_lfp", out_elems);
+        double *o_list = want_lists ? c->buf<double>(which == 1 ? "pred_out_csd_list" : "pred_out_lfp_list", out_elems * C)
+                                    : nullptr;
+        GemmDesc g5;                      // S[z][(r,i')] = sum_x' M1[z][x'] Bm[x'][(r,i')]
+        g5.M = nz; g5.N = (int)RT; g5.K = nx;
+        g5.A = M1 + (size_t)(which - 1) * nz * nx; g5.lda = nx; g5.B = Bm; g5.ldb = RT; g5.C = S; g5.ldc = RT;
+        g5.prof_name = "gemm_pred_cross";
+        gemm_f64(c, g5, s);
+        PredAtDesc pa;                    // out[cc][z][j][r] = sum_i' Pcat[i'][cc*ntstar + j] S[(z,r)][i'], and the sum over cc
+        pa.S = S; pa.lds = nt; pa.Pc = Pc; pa.ldp = (long)C * ntstar;
+        pa.K = nt; pa.nts = ntstar; pa.C = C; pa.R = R; pa.ncol = (long)nz * R;
+        pa.list = o_list; pa.list_stride = (long)out_elems; pa.sum = o_sum;
+        gemm_pred_at(c, pa, s);
+    }
+    // the resident outputs are this call's now: nothing queued earlier may be evaluated again over them (drain_async, the paired wait)
+    ++c->pred_seq;
+    c->last_pred.have = false;
+    return finish_call(c, e, nullptr, 0);
+}
+
+extern "C" int gpcsd_predict_at_resident(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar,
+                                         int ntstar, int type, int want_lists) {
+    GP_API_BEGIN(c)
+    return predict_at_impl(c, hp, z, nz, tstar, ntstar, type, want_lists != 0);
+    GP_API_END(c)
+}
+
+extern "C" int gpcsd_predict_at(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar,
+                                int type, double *csd_list, double *csd, double *lfp_list, double *lfp) {
+    GP_API_BEGIN(c)
+    const int rc = predict_at_impl(c, hp, z, nz, tstar, ntstar, type, csd_list != nullptr || lfp_list != nullptr);
+    if (rc < 0) return rc;
+    const size_t out_elems = (size_t)nz * ntstar * c->ntrials;
+    const int C = hp->n_temporal;
+    if (type & 1) {
+        if (csd) c->download(csd, c->bufs["pred_out_csd"].p, out_elems * sizeof(double));
+        if (csd_list) c->download(csd_list, c->bufs["pred_out_csd_list"].p, out_elems * C * sizeof(double));
+    }
+    if (type & 2) {
+        if (lfp) c->download(lfp, c->bufs["pred_out_lfp"].p, out_elems * sizeof(double));
+        if (lfp_list) c->download(lfp_list, c->bufs["pred_out_lfp_list"].p, out_elems * C * sizeof(double));
+    }
+    c->sync();
     return rc;
     GP_API_END(c)
 }

@@ -784,6 +784,236 @@ void gemm_pred_unfold(gpcsd_ctx *c, const PredUnfoldDesc &d, hipStream_t s) {
     GP_HIP(hipGetLastError());
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Last product of a prediction at arbitrary times (gpcsd_predict_at), written straight into the output layout:
+//
+//   out[cc][z][j][r] = sum_i' Pcat[i'][cc * nts + j] S[(z, r)][i']        sum[z][j][r] = sum over cc
+//
+// As gemm_pred_unfold_kernel the kernel computes the transposed product, rows = (cc, j), columns = (z, r), so that the lanes of
+// a wave run along r, the innermost index of the outputs, and every store instruction writes 16 consecutive trials (128 bytes)
+// of four prediction times.  A workgroup owns a 64 x 64 tile: 64 rows = CC components x 32 * BF times (fragment i of a wave =
+// component i / BF, so the sum over components is a register add in the epilogue), 64 columns (z, r).  Neither the
+// (z, r, cc, j) product nor a relayout pass over it exists: nothing of size C * nz * R * nts is allocated but the outputs.
+// A launch carries one or two components (CC x BF = 2 fragments of rows per wave either way); callers with more queue the
+// pairs one after the other, the later ones adding their partial sum to `sum` (accum).
+struct PredAtK {
+    const double *S;             // S [(z, r)][K] row-major
+    long lds;
+    const double *Pc;            // Pcat [K][C * nts]; column 0 = this launch's first component
+    long ldp;
+    int K, nts, R;
+    long ncol;                   // nz * R
+    double *list;                // [cc][z][j][r], this launch's first component (nullptr: sums only)
+    long list_stride;
+    double *sum;                 // [z][j][r]
+    int accum;                   // 1: sum += (components of an earlier launch are in it already)
+    int tiles_b;
+};
+
+template <int CC, int BF>
+__global__ __launch_bounds__(256) void gemm_pred_at_kernel(PredAtK g) {
+    constexpr int NT = 256, BK = 16, BB = 32 * BF, BM = BB * CC, BN = 64;
+    static_assert(BM == 64, "two row fragments per wave");
+    using TileA = Tile<BM, true, NT, BK>;     // Pcat: global [K][rows]
+    using TileB = Tile<BN, false, NT, BK>;    // S: global [cols][K]
+    __shared__ double lds[2 * (TileA::LDS_ELEMS + TileB::LDS_ELEMS)];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wr = wid >> 1, wc = wid & 1;
+    // XCD-aware order as in gemm_f64_kernel: consecutive logical tiles share the S panel (the long dimension)
+    int L = blockIdx.x;
+    {
+        const int total = gridDim.x;
+        if (total >= 64) {
+            const int x = L & 7, q = total >> 3, r = total & 7;
+            L = x * q + (x < r ? x : r) + (L >> 3);
+        }
+    }
+    const int tile_b = L % g.tiles_b;
+    const long tile_c = L / g.tiles_b;
+    const int j0 = tile_b * BB;
+    const long n0 = tile_c * BN;
+    const int fr = lane & 15, fq = lane >> 4;
+
+    d4 acc[CC * BF][2];                                        // [component * BF + time fragment][column fragment]
+#pragma unroll
+    for (int i = 0; i < CC * BF; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
+
+    int oa0, ka0, ob0, kb0;
+    TileA::slot0(tid, oa0, ka0);
+    TileB::slot0(tid, ob0, kb0);
+    double *const swA = lds + TileA::lds_index(oa0, ka0);
+    double *const swB = lds + 2 * TileA::LDS_ELEMS + TileB::lds_index(ob0, kb0);
+    using Buf0 = std::integral_constant<int, 0>;
+    using Buf1 = std::integral_constant<int, 1>;
+
+    const int K = g.K;
+    // per-thread slots: A slot i = (row o = oa0, k = ka0 + DK i), row o -> component o / BB, time j0 + o % BB (clamped: a
+    // duplicated edge row or column only feeds accumulators the epilogue never stores)
+    unsigned offA[TileA::PER_THREAD], offB[TileB::PER_THREAD];
+    int colA;
+    {
+        const int cc = oa0 / BB, jj = j0 + (oa0 % BB);
+        colA = cc * g.nts + (jj < g.nts ? jj : g.nts - 1);
+#pragma unroll
+        for (int i = 0; i < TileA::PER_THREAD; ++i) offA[i] = (unsigned)(((long)(ka0 + TileA::DK * i) * g.ldp + colA) * 8);
+    }
+    int relB[TileB::PER_THREAD];
+#pragma unroll
+    for (int i = 0; i < TileB::PER_THREAD; ++i) {
+        const long col = n0 + ob0 + TileB::DO * i;
+        relB[i] = (int)((col < g.ncol ? col : g.ncol - 1) - n0);
+        offB[i] = (unsigned)(((long)relB[i] * g.lds + kb0) * 8);
+    }
+    const double *const baseA = g.Pc;
+    const double *const baseB = g.S + n0 * g.lds;              // wave-uniform; 32-bit offsets span one 64-row tile only
+    const int nk = (K + BK - 1) / BK, nfull = K / BK;
+    double ra[TileA::PER_THREAD], rb[TileB::PER_THREAD];
+    const double *const srA = lds + TileA::lds_index(wr * 16 + fr, fq);
+    const double *const srB = lds + 2 * TileA::LDS_ELEMS + TileB::lds_index(wc * 16 + fr, fq);
+
+    auto load_full = [&](int t) {
+        TileA::gload(ra, TileA::rsrc(baseA, g.ldp, t), 0, offA);
+        TileB::gload(rb, TileB::rsrc(baseB, g.lds, t), 0, offB);
+    };
+    auto load_any = [&](int t) {
+        if (t < nfull) {
+            load_full(t);
+        } else {                                               // partial K tile: out-of-range k reads the last valid one
+            const int kleft = K - t * BK;
+            const __amdgpu_buffer_rsrc_t rsa = TileA::rsrc(baseA, g.ldp, t), rsb = TileB::rsrc(baseB, g.lds, t);
+#pragma unroll
+            for (int i = 0; i < TileA::PER_THREAD; ++i) {
+                const int kk = ka0 + TileA::DK * i, kc = kk < kleft ? kk : kleft - 1;
+                ra[i] = TileA::bload(rsa, (unsigned)(((long)kc * g.ldp + colA) * 8), 0);
+            }
+            const int kc = kb0 < kleft ? kb0 : kleft - 1;
+#pragma unroll
+            for (int i = 0; i < TileB::PER_THREAD; ++i) rb[i] = TileB::bload(rsb, (unsigned)(((long)relB[i] * g.lds + kc) * 8), 0);
+        }
+    };
+    auto store_any = [&](auto bufc, int t) {
+        constexpr int buf = decltype(bufc)::value;
+        if (t < nfull) {
+            TileA::template sstore<false>(ra, swA + buf * TileA::LDS_ELEMS, 0, 0);
+            TileB::template sstore<false>(rb, swB + buf * TileB::LDS_ELEMS, 0, 0);
+        } else {
+            TileA::template sstore<true>(ra, swA + buf * TileA::LDS_ELEMS, ka0, K - t * BK);
+            TileB::template sstore<true>(rb, swB + buf * TileB::LDS_ELEMS, kb0, K - t * BK);
+        }
+    };
+    const int last_steps = (nk > nfull) ? (K - nfull * BK + 3) / 4 : BK / 4;
+    auto mma = [&](auto bufc, int steps) {
+        constexpr int buf = decltype(bufc)::value;
+        const double *sa = srA + buf * TileA::LDS_ELEMS;
+        const double *sb = srB + buf * TileB::LDS_ELEMS;
+#pragma unroll
+        for (int kk = 0; kk < BK / 4; ++kk) {
+            if (kk < steps) {                                  // wave-uniform
+                double a[CC * BF], b[2];
+#pragma unroll
+                for (int i = 0; i < CC * BF; ++i) a[i] = LDS_FRAG(sa + TileA::lds_index(i * 32, kk * 4));
+#pragma unroll
+                for (int j = 0; j < 2; ++j) b[j] = LDS_FRAG(sb + TileB::lds_index(j * 32, kk * 4));
+#pragma unroll
+                for (int i = 0; i < CC * BF; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
+            }
+        }
+    };
+    load_any(0);
+    store_any(Buf0{}, 0);
+    __syncthreads();
+    int kt = 0;
+    for (; kt + 2 < nfull; kt += 2) {
+        load_full(kt + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        mma(Buf0{}, BK / 4);
+        __builtin_amdgcn_sched_barrier(0);
+        store_any(Buf1{}, kt + 1);
+        __syncthreads();
+        load_full(kt + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        mma(Buf1{}, BK / 4);
+        __builtin_amdgcn_sched_barrier(0);
+        store_any(Buf0{}, kt + 2);
+        __syncthreads();
+    }
+    if (kt + 1 < nk) {
+        load_any(kt + 1);
+        mma(Buf0{}, BK / 4);
+        store_any(Buf1{}, kt + 1);
+        __syncthreads();
+        if (kt + 2 < nk) {
+            load_any(kt + 2);
+            mma(Buf1{}, BK / 4);
+            store_any(Buf0{}, kt + 2);
+            __syncthreads();
+            mma(Buf0{}, last_steps);
+        } else {
+            mma(Buf1{}, last_steps);
+        }
+    } else {
+        mma(Buf0{}, last_steps);
+    }
+
+    // ---- epilogue: every component in the (z, j, r) layout, and their sum in index order ----
+    const long rowlen = (long)g.nts * g.R;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const long rho = n0 + j * 32 + wc * 16 + fr;           // this lane's column (z, r)
+        if (rho >= g.ncol) continue;
+        const long zz = rho / g.R;
+        const long base = zz * rowlen + (rho - zz * g.R);
+#pragma unroll
+        for (int f = 0; f < BF; ++f)
+#pragma unroll
+            for (int r4 = 0; r4 < 4; ++r4) {
+                const int jj = j0 + f * 32 + wr * 16 + fq + 4 * r4;
+                if (jj >= g.nts) continue;
+                const long o = base + (long)jj * g.R;
+                double sacc = 0.0;
+#pragma unroll
+                for (int cc = 0; cc < CC; ++cc) {
+                    const double v = acc[cc * BF + f][j][r4];
+                    sacc += v;
+                    if (g.list) g.list[(long)cc * g.list_stride + o] = v;      // wave-uniform
+                }
+                g.sum[o] = g.accum ? g.sum[o] + sacc : sacc;
+            }
+    }
+}
+
+void gemm_pred_at(gpcsd_ctx *c, const PredAtDesc &d, hipStream_t s) {
+    GP_REQUIRE(d.ncol > 0 && d.nts > 0 && d.K > 0 && d.C > 0 && d.R > 0, -3, "gemm_pred_at: empty problem");
+    // 32-bit byte offsets inside one K tile of one block tile: 16 rows of Pcat, 64 rows of S
+    GP_REQUIRE(d.ldp < GPCSD_MAX_GEMM_LD_KMAJOR && d.lds < (1L << 22), GPCSD_ERR_CAPACITY,
+               "gemm_pred_at: leading dimension %ld exceeds the capacity of one operand row", d.ldp < GPCSD_MAX_GEMM_LD_KMAJOR ? d.lds : d.ldp);
+    const long tiles_c = (d.ncol + 63) / 64;
+    GP_REQUIRE(tiles_c * (long)ceil_div(d.nts, 32) < (1L << 31), GPCSD_ERR_CAPACITY, "gemm_pred_at: too many tiles");
+    ProfScope ps(c, "gemm_pred_at", 2.0 * (double)d.ncol * d.C * (double)d.nts * d.K, s);
+    for (int c0 = 0; c0 < d.C; c0 += 2) {
+        PredAtK k;
+        k.S = d.S; k.lds = d.lds;
+        k.Pc = d.Pc + (long)c0 * d.nts; k.ldp = d.ldp;
+        k.K = d.K; k.nts = d.nts; k.R = d.R; k.ncol = d.ncol;
+        k.list = d.list ? d.list + (long)c0 * d.list_stride : nullptr;
+        k.list_stride = d.list_stride;
+        k.sum = d.sum;
+        k.accum = c0 > 0;
+        if (d.C - c0 >= 2) {
+            k.tiles_b = ceil_div(d.nts, 32);
+            hipLaunchKernelGGL((gemm_pred_at_kernel<2, 1>), dim3((unsigned)(k.tiles_b * tiles_c)), dim3(256), 0, s, k);
+        } else {
+            k.tiles_b = ceil_div(d.nts, 64);
+            hipLaunchKernelGGL((gemm_pred_at_kernel<1, 2>), dim3((unsigned)(k.tiles_b * tiles_c)), dim3(256), 0, s, k);
+        }
+        GP_HIP(hipGetLastError());
+    }
+}
+
 // Deterministic final reduction of per-block partials (single workgroup, fixed tree).
 // A second workgroup may carry an unrelated reduction of the same shape (p2, n2 -> out2: the sum of log D partials of the
 // likelihood, which would otherwise be a launch of its own in the dependent tail of the call).

@@ -86,6 +86,21 @@ constexpr int PRED_UNFOLD_BN = 32;      // columns (site orbit, trial) per tile 
 bool gemm_pred_unfold_supported(int C, long nrows_S, int nt);
 void gemm_pred_unfold(gpcsd_ctx *c, const PredUnfoldDesc &d, hipStream_t s);
 
+// Last product of a prediction at arbitrary times, written in the output layout with the component sum in its epilogue
+// (gemm_f64.hip: gemm_pred_at_kernel): out[cc][z][j][r] = sum_i Pc[i][cc * nts + j] S[(z, r)][i], sum[z][j][r] = sum over cc.
+struct PredAtDesc {
+    const double *S;                // [(z, r)][K] row-major
+    long lds;
+    const double *Pc;               // [K][C * nts]
+    long ldp;
+    int K, nts, C, R;
+    long ncol;                      // nz * R
+    double *list;                   // (C, nz, nts, R) or nullptr
+    long list_stride;
+    double *sum;                    // (nz, nts, R)
+};
+void gemm_pred_at(gpcsd_ctx *c, const PredAtDesc &d, hipStream_t s);
+
 // ---------------------------------------------------------------- batched hyper-parameter sets
 // Device image of gpcsd_hparams for batched evaluations (gpcsd_loglik_grad_batch): one entry per hyper-parameter set.  The
 // Gram builders / derivative kernels take an optional table: with `tab` they run once for all B sets (the set index is a grid

@@ -743,6 +743,37 @@ class GPCSDModel:
                 res = {k: sh.gather_trials(v) for k, v in res.items()}
         self._store_predictions(res, z, t)
 
+    def predict_at(self, z, tstar, type="csd", resident=False):
+        """Posterior mean of CSD and/or LFP at sites z and ARBITRARY times tstar (any length >= 1: up-sampling, a window, shifted
+        times) for every (local) trial; arguments, attributes, `resident` and trial sharding as `predict`, with `t_pred = tstar`.
+
+        Unlike `predict(z, t)`, which for t other than the training grid reproduces the reference's contraction of the test axis of
+        compute_Kt(t) (gpcsd1d.py:277-279), this contracts the training axis and so is the GP prediction at tstar; the two agree
+        when t is the training grid.  No reference counterpart."""
+        if type not in ("csd", "lfp", "both"):
+            raise ValueError("type must be 'csd', 'lfp' or 'both'")
+        ctx = self._sync_device()
+        z = np.asarray(z, dtype=np.float64)
+        z2 = z.reshape(-1, 1) if self.dim == 1 else z
+        tstar = np.asarray(tstar)
+        if tstar.size < 1:
+            raise ValueError("tstar must hold at least one time")
+        hp, _keep = self._hparams(0.0, tstar=tstar)        # no jitter, as predict
+        code = {"csd": _hip.PRED_CSD, "lfp": _hip.PRED_LFP, "both": _hip.PRED_BOTH}[type]
+        R_local = self._local_lfp().shape[2]
+        sh = getattr(self, "_sharding", None)
+        gather = sh is not None and getattr(sh, "gather_predictions", False)
+        if resident or (gather and sh.on_device()):
+            ctx.predict_resident(hp, z2, tstar, code, want_lists=True, at=True)
+            res = self._device_predictions(ctx, code, z2.shape[0], tstar.size, R_local)
+            if gather:
+                res = {k: sh.gather_trials_device(v, dst=getattr(sh, "gather_dst", None)) for k, v in res.items()}
+        else:
+            res = ctx.predict(hp, z2, tstar, code, (z2.shape[0], tstar.size, R_local), at=True)
+            if gather:
+                res = {k: sh.gather_trials(v) for k, v in res.items()}
+        self._store_predictions(res, z, tstar)
+
     def loglik_predict_many(self, param_sets, z, t, type="csd", resident=False, share_spatial=False):
         """loglik() and predict(z, t, type) under each of a LIST of hyper-parameter sets -- dicts as extract_model_params() returns
         them: the optima of every restart of a fit, a grid, posterior draws -- in order.  Returns the log-likelihoods, one per set;

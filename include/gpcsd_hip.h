@@ -277,6 +277,24 @@ int gpcsd_predict(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double *z, int 
  * (gpcsd_loglik*, gpcsd_predict, ...).  Argument errors (rc < 0) are still reported by the call itself. */
 int gpcsd_predict_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double *z, int nz,
                            const double *tstar, int ntstar, int type, int want_lists);
+/* Posterior mean at ARBITRARY prediction times: out_c[z, j, r] = sum_{x,i} Kcross[x, z] InvY_r[x, i] k_c(t*_j, t_i) with
+ * k_c(t*_j, t_i) = cov_c.compute_Kt(tstar)[j, i], the TRAINING axis i contracted; ntstar is any positive count (up-sampling, a
+ * window, times shifted against the grid).  NO REFERENCE COUNTERPART: the reference's predict reshapes compute_Kt(tstar) as if it
+ * were (nt, ntstar) (gpcsd1d.py:277-279), so it needs ntstar == nt and contracts the test axis of the cross Gram with the training
+ * axis of InvY -- a GP prediction only when tstar is the training grid, where Kt is symmetric.  gpcsd_predict reproduces that
+ * quirk bit for bit and keeps it; this call is the prediction itself, and equals gpcsd_predict (to rounding) when tstar == t.
+ * Arguments, `type`, NULL outputs and return codes as gpcsd_predict, except that no length is refused with -22; a capacity limit
+ * (ntrials * ntstar or n_temporal * ntstar >= GPCSD_MAX_GEMM_LD_KMAJOR) returns GPCSD_ERR_CAPACITY before tstar is read.
+ * Outputs: *_list (n_temporal, nz, ntstar, ntrials), sums (nz, ntstar, ntrials).  User-defined temporal covariances
+ * (GPCSD_KIND_HOST): hand compute_Kt(tstar) per component, (ncomp, ntstar, nt), to gpcsd_set_host_temporal_gram first. */
+int gpcsd_predict_at(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double *z, int nz,
+                     const double *tstar, int ntstar, int type,
+                     double *csd_list, double *csd, double *lfp_list, double *lfp);
+/* Same computation, results left in the named device buffers of gpcsd_predict_resident ("pred_out_csd", "pred_out_lfp":
+ * nz*ntstar*ntrials; "pred_out_csd_list", "pred_out_lfp_list": n_temporal times that, when want_lists) for gpcsd_fetch /
+ * gpcsd_device_buffer.  This call waits for its own work: a numerical failure (rc > 0) is returned by the call itself. */
+int gpcsd_predict_at_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double *z, int nz,
+                              const double *tstar, int ntstar, int type, int want_lists);
 /* copy `count` doubles of the named ctx-owned device buffer to host; rc -2 if the name is unknown; rc > 0 if the
  * asynchronous gpcsd_predict_resident that produced the buffer failed numerically */
 int gpcsd_fetch(gpcsd_ctx *ctx, const char *name, double *host, long count);
