@@ -427,12 +427,6 @@ struct EigState {
     } pa;
 };
 
-// Stage 5 instead of stage 3 (gpcsd_ctx::q_pipe): both halves whole in the register tail, the temporal product first in the
-// log-likelihood's tail (GPCSD_LL_ORDER=0), and the caller has promised to form X through loglik_tri_pre (x_via_tri_pre).
-static int ll_order() {                    // GPCSD_LL_ORDER: order of the log-likelihood's two products (capi_fused.inl)
-    static const int o = getenv("GPCSD_LL_ORDER") ? atoi(getenv("GPCSD_LL_ORDER")) : 0;
-    return o;
-}
 // Stage 5's kernels form T and Q for every tridiagonal-form consumer they can hold (both halves whole in the register tail, and
 // only where a prediction takes the tridiagonal form as well: a chain with an eigenvector-form consumer keeps stage 3 -- its stage
 // 4 reads stage 3's T factors) -- pipelined under stage 1 or not, so that Q, X and everything after them have the same bits
@@ -441,10 +435,9 @@ static bool q_stage5_applies(const gpcsd_ctx *c, const SymDev *sym_t) {
     return sym_t && std::max(sym_t->ns, sym_t->na) <= eigh_regtail_rows() &&
            k_tridiag_solve_pass(std::max(sym_t->ns, sym_t->na), c->ntrials) > 0;
 }
-// ... and pipelined (gpcsd_ctx::q_pipe) when the caller has promised to form X through loglik_tri_pre (x_via_tri_pre) with the
-// temporal product first in the log-likelihood's tail (GPCSD_LL_ORDER=0)
+// ... and pipelined (gpcsd_ctx::q_pipe) when the caller has promised to form X through loglik_tri_pre (x_via_tri_pre)
 static bool q_pipe_applies(const gpcsd_ctx *c, const SymDev *sym_t, bool x_via_tri_pre) {
-    return c->q_pipe && x_via_tri_pre && ll_order() == 0 && q_stage5_applies(c, sym_t);
+    return c->q_pipe && x_via_tri_pre && q_stage5_applies(c, sym_t);
 }
 
 // Queue stage 5 (EigState::pipe_pending): on stream4, behind ev_t0, T factor and forward apply panel by panel under the running

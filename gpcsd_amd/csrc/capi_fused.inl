@@ -30,11 +30,6 @@ static int finish_loglik_async(gpcsd_ctx *c, const EigState &e, bool two, bool s
 // Shifted-tridiagonal form (EigState::tri): X = Y~ Q needs stage 1 of the temporal chain only and is queued BEFORE the main
 // stream waits for the spatial chain; after that wait W = diag(U)^T X, and one forward recurrence per row gives the quadratic
 // form, the pivots the log-determinant (k_ll_tridiag).  The temporal eigenvectors are never read.
-// Order of the log-likelihood's two products: X = Y~ Q then W = U^T X (0: the temporal product first, behind Q and in front of the
-// wait for the spatial chain), or W0 = U^T Y~ then W = W0 Q (1: the spatial product first, behind the spatial chain and in front
-// of the wait for Q).  Same flops, same shapes; whichever chain ends first should have its product first.  GPCSD_LL_ORDER.
-// (ll_order(): capi.hip, beside q_pipe_applies)
-
 // out[(x, r)][t~ block p] = in[(x, r)][t~ block p] Q_p, both parity blocks in one launch (Q of replica e.tri_rep; waits for stage 3)
 static void tri_times_Q(gpcsd_ctx *c, EigState &e, const FoldMode &fm, const double *in, double *out, const char *prof) {
     const int nx = c->nx, nt = c->nt, R = c->ntrials;
@@ -54,45 +49,49 @@ static void tri_times_Q(gpcsd_ctx *c, EigState &e, const FoldMode &fm, const dou
     gemm_pair(c, g[0], g[1], s);
 }
 
-static void loglik_tri_pre(gpcsd_ctx *c, EigState &e, const FoldMode &fm, const double *Yf, const char *xname = "ll_X",
-                           const char *prof = "gemm_ll_YQ", bool is_ll = true) {
-    if (is_ll && ll_order() == 1) return;              // spatial product first: everything happens in the tail
+// X = Y~ Q of a tridiagonal-form consumer: the log-likelihood's (pred == null) or that prediction's own
+static void loglik_tri_pre(gpcsd_ctx *c, EigState &e, const FoldMode &fm, const double *Yf, const PredCall *pred) {
+    const char *xname = pred ? "pred_X" : "ll_X";
     if (e.pipe_pending) {                              // stage 1 ran with progress words: T, Q and X panel by panel (queue_q_pipeline)
         queue_q_pipeline(c, e, Yf, xname);
         return;
     }
-    tri_times_Q(c, e, fm, Yf, c->buf<double>(xname, (size_t)c->nx * c->ntrials * c->nt), prof);
+    tri_times_Q(c, e, fm, Yf, c->buf<double>(xname, (size_t)c->nx * c->ntrials * c->nt), pred ? "gemm_pred_YQ" : "gemm_ll_YQ");
+}
+
+// The shifted tridiagonal systems of replica e.tri_rep.  Behind a pipelined stage 5 nothing on the stream is ordered behind the END
+// of stage 1 yet (d, e, the scale): their first reader's wait is queued here.
+struct TriOperands {
+    const double *d[2], *e[2], *amax[2];
+    int np[2], c0[2];
+};
+static TriOperands tri_operands(gpcsd_ctx *c, const EigState &e, const FoldMode &fm, hipStream_t s) {
+    TriOperands o;
+    const char *const *tg = eigh_fold_tags(c, 1);
+    for (int p = 0; p < 2; ++p) {
+        o.np[p] = p ? fm.ft.na : fm.ft.ns;
+        o.c0[p] = p ? fm.ft.ns : 0;
+        const EigArenaView av = eigh_arena_view(c, tg[p], o.np[p], e.tri_count);
+        const long off = (long)e.tri_rep * av.blk;
+        o.d[p] = av.d + off; o.e[p] = av.e + off; o.amax[p] = av.amax + off;
+    }
+    if (c->t1_wait_pending) {
+        GP_HIP(hipStreamWaitEvent(s, c->ev_t1, 0));
+        c->t1_wait_pending = false;
+    }
+    return o;
 }
 
 // host_slot: the caller's pinned result slot when the evaluation is asynchronous (else null); returns true when the tail wrote it
-static bool loglik_tri_tail(gpcsd_ctx *c, EigState &e, const FoldMode &fm, const double *Yf, double *W, double *host_slot = nullptr) {
+static bool loglik_tri_tail(gpcsd_ctx *c, EigState &e, const FoldMode &fm, double *W, double *host_slot = nullptr) {
     const int nx = c->nx, nt = c->nt, R = c->ntrials;
     hipStream_t s = c->stream;
     ++c->fold_gemm_calls;
     ++c->ll_tridiag_calls;
     join_spatial(c, e);
-    double *X = c->buf<double>("ll_X", (size_t)nx * R * nt);
-    if (ll_order() == 1) {
-        fold_proj_spatial(c, fm.fs, Yf, X, (long)R * nt, s);
-        tri_times_Q(c, e, fm, X, W, "gemm_ll_WQ");
-    } else {
-        fold_proj_spatial(c, fm.fs, X, W, (long)R * nt, s);
-    }
-    const char *const *tg = eigh_fold_tags(c, 1);
-    const double *d[2], *ee[2], *am[2];
-    int np[2], c0[2];
-    for (int p = 0; p < 2; ++p) {
-        np[p] = p ? fm.ft.na : fm.ft.ns;
-        c0[p] = p ? fm.ft.ns : 0;
-        const EigArenaView av = eigh_arena_view(c, tg[p], np[p], e.tri_count);
-        const long o = (long)e.tri_rep * av.blk;
-        d[p] = av.d + o; ee[p] = av.e + o; am[p] = av.amax + o;
-    }
-    if (c->t1_wait_pending) {              // stage 5: nothing on this stream is ordered behind the END of stage 1 yet (d, e, the scale)
-        GP_HIP(hipStreamWaitEvent(s, c->ev_t1, 0));
-        c->t1_wait_pending = false;
-    }
-    const bool wrote = k_ll_tridiag(c, W, fm.fs.w, d, ee, am, e.d_sig, nx, R, nt, np, c0, e.scal, e.scal + 1, s, host_slot,
+    fold_proj_spatial(c, fm.fs, c->buf<double>("ll_X", (size_t)nx * R * nt), W, (long)R * nt, s);
+    const TriOperands o = tri_operands(c, e, fm, s);
+    const bool wrote = k_ll_tridiag(c, W, fm.fs.w, o.d, o.e, o.amax, e.d_sig, nx, R, nt, o.np, o.c0, e.scal, e.scal + 1, s, host_slot,
                                     e.scal + gpcsd_ctx::SCAL_N, gpcsd_ctx::SCAL_N, gpcsd_ctx::RESULT_DOUBLES - gpcsd_ctx::SCAL_N);
     GP_HIP(hipEventRecord(c->ev_tri_done[c->tgen], s));
     c->tri_reader_queued[c->tgen] = true;
@@ -104,8 +103,8 @@ static bool loglik_fold_tail(gpcsd_ctx *c, EigState &e, const FoldMode &fm, cons
     const int nx = c->nx, nt = c->nt, R = c->ntrials;
     hipStream_t s = c->stream;
     if (e.tri) {
-        loglik_tri_pre(c, e, fm, Yf);
-        const bool wrote = loglik_tri_tail(c, e, fm, Yf, W, host_slot);
+        loglik_tri_pre(c, e, fm, Yf, nullptr);
+        const bool wrote = loglik_tri_tail(c, e, fm, W, host_slot);
         if (slot_written) *slot_written = wrote;
         return true;
     }
@@ -175,6 +174,15 @@ static int loglik_parts_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, double *out2
     return finish_call(c, e, out2, 2);
 }
 
+// clean status words for whatever is queued from here on (everything has been drained: nobody reports into them now)
+static void clear_status_words(gpcsd_ctx *c) {
+    if (int *dst = reinterpret_cast<int *>(c->buf<double>("scal_status", gpcsd_ctx::RESULT_DOUBLES) + gpcsd_ctx::SCAL_N)) {
+        GP_HIP(hipMemsetAsync(dst, 0, gpcsd_ctx::STATUS_N * sizeof(int), c->stream));
+        GP_HIP(hipStreamSynchronize(c->stream));
+        c->status_zeroed = true;
+    }
+}
+
 // Status 7 is not a numerical failure: a gate of the pipelined stage 5 (wy.hip: wy_qstage_kernel) gave up waiting for the
 // tridiagonalisation that should have been running beside it -- kernels serialised by a profiler or a debugger, an oversubscribed
 // card, a tail that could not get a CU.  The launch did nothing with the unfinished reflectors, so the evaluation is void, not
@@ -186,25 +194,47 @@ static bool q_pipe_missed(gpcsd_ctx *c, int rc, bool piped) {
     c->q_pipe = false;
     ++c->q_pipe_timeouts;
     drain_after_failure(c);                // (also drops an announced front half: it was queued with the pipeline on)
-    if (int *dst = reinterpret_cast<int *>(c->buf<double>("scal_status", gpcsd_ctx::RESULT_DOUBLES) + gpcsd_ctx::SCAL_N)) {
-        GP_HIP(hipMemsetAsync(dst, 0, gpcsd_ctx::STATUS_N * sizeof(int), c->stream));
-        GP_HIP(hipStreamSynchronize(c->stream));
-        c->status_zeroed = true;
-    }
+    clear_status_words(c);
     c->last_error.clear();
     return true;
 }
 
-static void keep_prediction(gpcsd_ctx *c, bool piped, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar,
-                            int type, bool want_lists) {
+static int predict_impl(gpcsd_ctx *c, const PredCall &q);
+static void sink_release(gpcsd_ctx *c, PredSink *sk);
+
+// The one routine every collecting call goes through (q_pipe_missed's only caller): `rc` is what the call found for an evaluation
+// queued with the pipeline on or off (`piped`).  A scheduling miss is answered by evaluating again, unpipelined now, what the
+// collecting call owns -- the log-likelihood at `ll_hp` into out2 (null: none), the prediction `pred` (null: none, or no longer the
+// owner of the resident outputs), both for a pair: rc becomes that evaluation's status and the return value is true.
+static bool replay_if_missed(gpcsd_ctx *c, int &rc, bool piped, const gpcsd_hparams *ll_hp, double *out2, const PredCall *pred) {
+    if (!q_pipe_missed(c, rc, piped)) return false;
+    rc = 0;
+    if (ll_hp) rc = loglik_parts_impl(c, ll_hp, out2, false);
+    if (rc == 0 && pred) {
+        PredCall again = *pred;
+        again.async = false;
+        sink_release(c, again.sink);  // (gpcsd_predict: the copies of the void evaluation have landed before the next ones start)
+        rc = predict_impl(c, again);
+    }
+    return true;
+}
+
+// The request of a queued prediction, kept with copies of what it points to until another prediction owns the resident outputs
+static void keep_prediction(gpcsd_ctx *c, bool piped, const PredCall &q) {
     gpcsd_ctx::PredKeep &k = c->last_pred;
     ++c->pred_seq;
     k.have = true;
     k.piped = piped;
-    k.hp.set(hp);
-    k.z.assign(z, z + (size_t)nz * c->dim);
-    k.ts.assign(tstar, tstar + ntstar);
-    k.nz = nz; k.nts = ntstar; k.type = type; k.lists = want_lists;
+    k.hp.set(q.hp);
+    k.z.assign(q.z, q.z + (size_t)q.nz * c->dim);
+    k.ts.assign(q.tstar, q.tstar + q.ntstar);
+    k.call = q;
+    k.call.hp = &k.hp.hp; k.call.z = k.z.data(); k.call.tstar = k.ts.data();
+    k.call.sink = nullptr; k.call.ll = nullptr; k.call.prelude_side = false; k.call.solve_pass = 0;     // (of the queued call alone)
+}
+// ... for the call that collects slot sl: null unless the slot's paired prediction still owns the resident outputs
+static const PredCall *kept_prediction(const gpcsd_ctx *c, const gpcsd_ctx::LlSlot &sl) {
+    return (sl.pred_seq >= 0 && sl.pred_seq == c->pred_seq && c->last_pred.have) ? &c->last_pred.call : nullptr;
 }
 
 extern "C" int gpcsd_loglik_parts(gpcsd_ctx *c, const gpcsd_hparams *hp, double *out2) {
@@ -212,7 +242,7 @@ extern "C" int gpcsd_loglik_parts(gpcsd_ctx *c, const gpcsd_hparams *hp, double 
     GP_REQUIRE(out2 != nullptr, -3, "null output");
     const bool piped = c->q_pipe;
     int rc = loglik_parts_impl(c, hp, out2, false);
-    if (q_pipe_missed(c, rc, piped)) rc = loglik_parts_impl(c, hp, out2, false);
+    replay_if_missed(c, rc, piped, hp, out2, nullptr);
     return rc;
     GP_API_END(c)
 }
@@ -222,16 +252,15 @@ extern "C" int gpcsd_loglik_parts_async(gpcsd_ctx *c, const gpcsd_hparams *hp) {
         return fail(c, HipError{-3, "loglik_parts_async: too many asynchronous evaluations outstanding (collect with "
                                     "gpcsd_loglik_parts_wait)"});
     GP_API_BEGIN(c)
+    GP_REQUIRE(c->d_lfp != nullptr, -4, "lfp not set (call gpcsd_set_lfp)");
+    check_hp(c, hp, c->nx);              // before anything of hp is copied into the slot (HpKeep::set reads n_sig2n doubles)
     gpcsd_ctx::LlSlot &sl = c->ll_slot[(c->ll_head + c->ll_count) % gpcsd_ctx::LL_SLOTS];
     sl.piped = c->q_pipe;
     sl.pred_seq = -1;
-    if (hp) sl.hp.set(hp);
+    sl.hp.set(hp);
     return loglik_parts_impl(c, hp, nullptr, true);
     GP_API_END(c)
 }
-
-static int predict_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar,
-                        int type, bool want_lists, bool async);
 
 extern "C" int gpcsd_loglik_parts_wait(gpcsd_ctx *c, double *out2) {
     if (c && (!out2 || c->ll_count == 0))
@@ -241,23 +270,13 @@ extern "C" int gpcsd_loglik_parts_wait(gpcsd_ctx *c, double *out2) {
     gpcsd_ctx::LlSlot &sl = c->ll_slot[k];
     c->ll_head = (k + 1) % gpcsd_ctx::LL_SLOTS;
     --c->ll_count;
-    if (sl.done) {
+    if (sl.done) {                        // fenced profiling: evaluated when it was queued
         out2[0] = sl.out[0];
         out2[1] = sl.out[1];
+        replay_if_missed(c, sl.rc, sl.piped, &sl.hp.hp, out2, kept_prediction(c, sl));
         return sl.rc;
     }
-    {
-        // GPCSD_LL_WAIT=spin: poll the event instead of blocking in hipEventSynchronize (A/B for DESIGN 6's stall: does a blocked
-        // host wait miss its wake-up?)
-        static const bool spin = getenv("GPCSD_LL_WAIT") && !strcmp(getenv("GPCSD_LL_WAIT"), "spin");
-        if (spin) {
-            hipError_t q;
-            while ((q = hipEventQuery(sl.ev)) == hipErrorNotReady) {}
-            if (q != hipSuccess) GP_HIP(q);
-        } else {
-            GP_HIP(hipEventSynchronize(sl.ev));
-        }
-    }
+    GP_HIP(hipEventSynchronize(sl.ev));
     const double *host = c->h_ll + gpcsd_ctx::RESULT_DOUBLES * k;
     out2[0] = host[0];
     out2[1] = sl.two ? host[1] + host[2] : host[1];
@@ -265,33 +284,20 @@ extern "C" int gpcsd_loglik_parts_wait(gpcsd_ctx *c, double *out2) {
     memcpy(st, host + gpcsd_ctx::SCAL_N, sizeof(st));
     // (asynchronous calls: every word as it stood when this evaluation's copy ran, the late stages' of EARLIER chains included)
     const int bad = fold_status(st, true);
-    if (bad != 0) {                       // this evaluation's, or an earlier asynchronous call's that nobody collected yet
-        char b[160];
-        snprintf(b, sizeof(b), "numerical failure (status %d): eigensolver did not converge or matrix not positive definite", bad);
-        c->last_error = b;
-        // The status words are sticky while asynchronous work is outstanding (nobody may clear them under a running chain).
-        // Now that a failure has been reported: drain everything and clear them, so that evaluations queued from here on
-        // start clean.  Evaluations that were ALREADY outstanding copied the words as they stood and report the failure too
-        // (a failed wait poisons the ones queued before it returned; documented in gpcsd_hip.h).
-        if (q_pipe_missed(c, bad, sl.piped)) {
-            // a scheduling miss of the pipelined stage 5, not a failure: this evaluation again (unpipelined now), and the paired
-            // prediction with it when it is still the one that owns the resident outputs
-            int rc = loglik_parts_impl(c, &sl.hp.hp, out2, false);
-            if (rc == 0 && sl.pred_seq >= 0 && sl.pred_seq == c->pred_seq && c->last_pred.have) {
-                const gpcsd_ctx::PredKeep &k = c->last_pred;
-                rc = predict_impl(c, &k.hp.hp, k.z.data(), k.nz, k.ts.data(), k.nts, k.type, k.lists, false);
-            }
-            return rc;
-        }
-        drain_after_failure(c);
-        if (int *dst = reinterpret_cast<int *>(c->buf<double>("scal_status", gpcsd_ctx::RESULT_DOUBLES) + gpcsd_ctx::SCAL_N)) {
-            GP_HIP(hipMemsetAsync(dst, 0, gpcsd_ctx::STATUS_N * sizeof(int), c->stream));
-            GP_HIP(hipStreamSynchronize(c->stream));
-            c->status_zeroed = true;
-        }
-        return bad > 0 ? bad : 1;
-    }
-    return 0;
+    if (bad == 0) return 0;
+    // this evaluation's, or an earlier asynchronous call's that nobody collected yet
+    char b[160];
+    snprintf(b, sizeof(b), "numerical failure (status %d): eigensolver did not converge or matrix not positive definite", bad);
+    c->last_error = b;
+    int rc = bad;
+    if (replay_if_missed(c, rc, sl.piped, &sl.hp.hp, out2, kept_prediction(c, sl))) return rc;     // not a failure: evaluated again
+    // The status words are sticky while asynchronous work is outstanding (nobody may clear them under a running chain).
+    // Now that a failure has been reported: drain everything and clear them, so that evaluations queued from here on
+    // start clean.  Evaluations that were ALREADY outstanding copied the words as they stood and report the failure too
+    // (a failed wait poisons the ones queued before it returned; documented in gpcsd_hip.h).
+    drain_after_failure(c);
+    clear_status_words(c);
+    return bad > 0 ? bad : 1;
     GP_API_END(c)
 }
 
@@ -315,23 +321,141 @@ static const SymDev &site_symmetry(gpcsd_ctx *c, const double *z, int nz, int di
     return c->sym_z;
 }
 
-static bool pred_unfold_chunked(gpcsd_ctx *c, PredUnfoldDesc pu, int which0, int nz, size_t out_elems, bool want_lists, hipStream_t s);
+// The host outputs of gpcsd_predict (the class API's predict(), gpcsd1d.py:286-293: the arrays ARE the result), a local of that call:
+// the caller's arrays, which of them the chunked copy-out has filled (done), and the events it took from the pool.
+static void sink_release(gpcsd_ctx *c, PredSink *sk);
+struct PredSink {
+    bool active = false;                  // every array is page-locked: a folded prediction may copy out under its last product
+    double *sum[2] = {nullptr, nullptr}, *list[2] = {nullptr, nullptr};       // [0] csd, [1] lfp
+    bool done[2] = {false, false};
+    std::vector<hipEvent_t> events;
+    gpcsd_ctx *owner = nullptr;           // gpcsd_predict: the end of the call releases (normal end, negative code, exception)
+    ~PredSink() { sink_release(owner, this); }
+};
+// The one place that waits for the copies on stream4 and gives the events back; a replay comes here too (the outputs are then to
+// be filled again).
+static void sink_release(gpcsd_ctx *c, PredSink *sk) {
+    if (!c || !sk) return;
+    (void)hipStreamSynchronize(c->stream4);
+    c->event_pool.insert(c->event_pool.end(), sk->events.begin(), sk->events.end());
+    sk->events.clear();
+    sk->done[0] = sk->done[1] = false;
+}
+
+// The paired call's log-likelihood (gpcsd_loglik_predict_async), whose products predict_fold queues among its own
+struct PairLl {
+    EigState *e;
+    const FoldMode *fm;
+    bool share_x, share_w;                // the prediction reads the log-likelihood's X = Y~ Q / its W~ = diag(U)^T X instead of forming its own
+};
+
+static PredCall pred_call(const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar, int type, bool lists, bool async) {
+    PredCall q;
+    q.hp = hp; q.z = z; q.nz = nz; q.tstar = tstar; q.ntstar = ntstar; q.type = type; q.want_lists = lists; q.async = async;
+    return q;
+}
+static void check_predict_args(const gpcsd_ctx *c, const PredCall &q) {
+    GP_REQUIRE(q.z && q.tstar && q.nz > 0 && q.ntstar > 0, -3, "predict: bad arguments");
+    GP_REQUIRE(q.type >= 1 && q.type <= 3, -3, "predict: type must be CSD(1), LFP(2) or BOTH(3)");
+    GP_REQUIRE(c->nt > 0 && q.ntstar == c->nt, -22,
+               "predict: len(t)=%d must equal the training nt=%d (the reference's reshape raises ValueError, gpcsd1d.py:279)",
+               q.ntstar, c->nt);
+    GP_REQUIRE(c->d_lfp != nullptr, -4, "lfp not set (call gpcsd_set_lfp)");
+}
+
+// Which form a prediction takes, decided before anything is queued.  A folded side needs its outputs on a grid with the same
+// symmetry (t* = t; mirror-symmetric sites); an unfolded side takes any sites / times.
+struct PredPlan {
+    enum Form { FULL, FOLD_T, FOLD } form = FULL;      // full size; temporal side folded, spatial side unfolded; folded on both sides
+    bool fold_s() const { return form == FOLD; }
+    bool tri = false;           // in the basis U (x) Q (predict_tridiag_applies)
+    FoldMode fm;                // the decision; the caller takes the views again once its front half has started their generation
+    SymDev sz;                  // the sites' orbit tables (identity for an unfolded spatial side)
+    const double *Yf = nullptr, *dz = nullptr, *dts = nullptr;      // pred_operands
+};
+static PredPlan pred_plan(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar) {
+    PredPlan P;
+    P.fm = fold_mode(c, hp);
+    const bool t_ok = P.fm.on && ntstar == c->nt &&
+                      (!P.fm.ft.on || ((int)c->time_host.size() == c->nt &&
+                                       memcmp(c->time_host.data(), tstar, (size_t)ntstar * sizeof(double)) == 0));
+    if (!t_ok) return P;
+    P.sz = P.fm.fs.on ? site_symmetry(c, z, nz, c->dim) : identity_sym(c, nz);
+    P.form = PredPlan::FOLD;
+    // sites without the electrodes' symmetry (the reference's own use: four off-grid depths): the spatial side unfolded, the
+    // temporal side folded as ever -- not the full-size path
+    if (!(P.sz.ns > 0 && P.sz.ns + P.sz.na == nz) && P.fm.fs.on && P.fm.ft.on) {
+        P.form = PredPlan::FOLD_T;
+        P.sz = identity_sym(c, nz);
+    }
+    if (!(P.sz.ns > 0 && P.sz.ns + P.sz.na == nz)) P.form = PredPlan::FULL;
+    else P.tri = P.fm.ft.on && predict_tridiag_applies(P.fm.ft.ns, P.fm.ft.na, c->ntrials);
+    return P;
+}
+// Behind the front half of a folded prediction: the views of the generation it started (fm), the folded data, and this call's sites
+// and times on the device.  Returns true when sites or times had to be uploaded just now (on the main stream).
+static bool pred_operands(gpcsd_ctx *c, const PredCall &q, PredPlan &P, const FoldMode &fm) {
+    P.fm = fm;
+    P.Yf = folded_lfp(c, fm);
+    const long up0 = c->upload_count;
+    P.dz = c->upload_cached<double>("pred_z", q.z, (size_t)q.nz * c->dim);
+    P.dts = c->upload_cached<double>("pred_tstar", q.tstar, q.ntstar);
+    return c->upload_count != up0;
+}
+
+// The resident outputs of output `which` (1 csd, 2 lfp): the sum, and the per-component list when wanted
+struct PredOut {
+    double *sum, *list;
+};
+static PredOut pred_out_bufs(gpcsd_ctx *c, int which, size_t out_elems, int C, bool want_lists) {
+    return {c->buf<double>(which == 1 ? "pred_out_csd" : "pred_out_lfp", out_elems),
+            want_lists ? c->buf<double>(which == 1 ? "pred_out_csd_list" : "pred_out_lfp_list", out_elems * C) : nullptr};
+}
+// ... into the caller's arrays (those of `sk` that are not null and that the chunked copy-out has not filled already)
+static void pred_download(gpcsd_ctx *c, const PredCall &q, const PredSink &sk) {
+    const size_t out_elems = (size_t)q.nz * q.ntstar * c->ntrials;
+    for (int w = 0; w < 2; ++w) {
+        if (!(q.type & (w + 1)) || sk.done[w]) continue;
+        if (sk.sum[w]) c->download(sk.sum[w], c->bufs[w ? "pred_out_lfp" : "pred_out_csd"].p, out_elems * sizeof(double));
+        if (sk.list[w])
+            c->download(sk.list[w], c->bufs[w ? "pred_out_lfp_list" : "pred_out_csd_list"].p, out_elems * q.hp->n_temporal * sizeof(double));
+    }
+}
+
+static bool pred_unfold_chunked(gpcsd_ctx *c, const PredCall &q, PredUnfoldDesc pu, int which0, size_t out_elems, hipStream_t s);
+
+// The paired call's log-likelihood behind the wait for the spatial chain: its whole tail, in front of everything of the prediction that
+// needs a decomposition -- it is what the caller waits for -- and the copy of its result into the next slot.
+static void pair_ll_tail(gpcsd_ctx *c, const PairLl &ll, const double *Yf) {
+    double *Wll = c->buf<double>("proj_W_ll", (size_t)c->nx * c->ntrials * c->nt);
+    bool batched = true, wrote = false;
+    if (ll.e->tri) wrote = loglik_tri_tail(c, *ll.e, *ll.fm, Wll, next_ll_slot(c));
+    else batched = loglik_fold_tail(c, *ll.e, *ll.fm, Yf, Wll);
+    (void)finish_loglik_async(c, *ll.e, !batched, wrote);
+}
 
 // predict_impl in the folded basis (see FoldMode).  Prediction sites and times must share the symmetry of the grids:
 //   out_c = Fz^T [ diag_p( (Kc_pp^T U_p) ) Bm~ diag_q( V_q^T Kt*_c,qq ) ] Ft   with Bm~ = (diag(U)^T Y~ diag(V)) / D~ ,
 // every flat GEMM split in its two parity blocks; the last pass unfolds sites and times while it transposes.
-static int predict_fold(gpcsd_ctx *c, const gpcsd_hparams *hp, EigState &e, const FoldMode &fm, const double *Yf, const SymDev &sz,
-                        const double *dz, int nz, const double *dts, int type, bool want_lists, bool async,
-                        const std::function<void()> *after_spatial_join = nullptr,
-                        const std::function<void()> *before_spatial_join = nullptr, const char *shared_x = nullptr,
-                        bool prelude_side = false, const char *shared_w = nullptr) {
+static int predict_fold(gpcsd_ctx *c, const PredCall &q, const PredPlan &P, EigState &e) {
+    const gpcsd_hparams *hp = q.hp;
+    const FoldMode &fm = P.fm;
+    const SymDev &sz = P.sz;
+    const double *Yf = P.Yf, *dz = P.dz, *dts = P.dts;
+    const int nz = q.nz, type = q.type;
+    const bool want_lists = q.want_lists, prelude_side = q.prelude_side;
     const Geo g = resident_geo(c);
     const int nx = c->nx, nt = c->nt, R = c->ntrials, C = hp->n_temporal;
     const long RT = (long)R * nt;
     const int ns = fm.fs.ns, na = fm.fs.na, nts = fm.ft.ns, nta = fm.ft.na, nzs = sz.ns, nza = sz.na;
     hipStream_t s = c->stream;
-    // shared_w (the paired call with X and the spatial eigenvectors shared): W~ = diag(U)^T X is the log-likelihood's own product
-    double *W = c->buf<double>(shared_w ? shared_w : "proj_W", (size_t)nx * RT);
+    // The paired call (q.ll) with equal temporal hyper-parameters (share_x): X = Y~ Q is the log-likelihood's own product -- the two
+    // replicas of the temporal problem are the same matrix, decomposed by the same deterministic launches into the same bits, so a
+    // second product would only recompute it (0.1 ms of MFMA time and 154 MB of traffic per cfg3 step).  With the spatial
+    // eigenvectors shared as well (share_w): W~ = diag(U)^T X is the log-likelihood's too.  The buffers those flags select:
+    const bool shared_x = q.ll && q.ll->share_x, shared_w = q.ll && q.ll->share_w;
+    const char *xname = shared_x ? "ll_X" : "pred_X", *wname = shared_w ? "proj_W_ll" : "proj_W";
+    double *W = c->buf<double>(wname, (size_t)nx * RT);
     double *Bm = c->buf<double>("pred_B", (size_t)nx * RT);
     const double *t = (const double *)c->bufs["time_t"].p;
     double *Kc = c->buf<double>("pred_Kcross", (size_t)nx * nz);
@@ -373,22 +497,16 @@ static int predict_fold(gpcsd_ctx *c, const gpcsd_hparams *hp, EigState &e, cons
                         Ktf + cc * ktf_sz + (size_t)nts * nts, sp);
     }
     if (prelude_side) GP_HIP(hipEventRecord(c->ev_prelude, sp));
-    // then everything that needs only the spatial eigenvectors, beside the temporal eigensolver
-    if (before_spatial_join) (*before_spatial_join)();
-    // tridiagonal form (EigState::tri): X = Y~ Q needs the temporal tridiagonalisation + Q only and is queued in front of the wait
-    // for the spatial chain, exactly as the log-likelihood's
-    // (a call of its own: in front of the wait for the spatial chain; in the paired call: behind the log-likelihood's tail -- in
-    // front of it the product delays the result the caller is waiting for by its 0.09 ms)
-    // shared_x (the paired call with equal temporal hyper-parameters): X = Y~ Q is the log-likelihood's own product -- the two
-    // replicas of the temporal problem are the same matrix, decomposed by the same deterministic launches into the same bits, so
-    // the second product would only recompute `shared_x` (0.1 ms of MFMA time and 154 MB of traffic per cfg3 step)
-    const char *xname = shared_x ? shared_x : "pred_X";
-    if (e.tri && !after_spatial_join && !shared_x) loglik_tri_pre(c, e, fm, Yf, "pred_X", "gemm_pred_YQ", false);
+    // then everything that needs only the spatial eigenvectors, beside the temporal eigensolver.  In the tridiagonal form (EigState::tri)
+    // X = Y~ Q needs the temporal tridiagonalisation + Q only and is queued in front of the wait for the spatial chain -- the
+    // log-likelihood's in the paired call, this call's own otherwise
+    if (q.ll && q.ll->e->tri) loglik_tri_pre(c, *q.ll->e, *q.ll->fm, Yf, nullptr);
+    if (e.tri && !q.ll) loglik_tri_pre(c, e, fm, Yf, &q);
     join_spatial(c, e);
-    // gpcsd_loglik_predict_async: the log-likelihood's whole tail goes here, in front of everything of predict that needs a
-    // decomposition -- it is what the caller waits for
-    if (after_spatial_join) (*after_spatial_join)();
-    if (e.tri && after_spatial_join && !shared_x) loglik_tri_pre(c, e, fm, Yf, "pred_X", "gemm_pred_YQ", false);
+    if (q.ll) pair_ll_tail(c, *q.ll, Yf);
+    // (the paired call's own X: behind the log-likelihood's tail -- in front of it the product delays the result the caller is waiting
+    // for by its 0.09 ms)
+    if (e.tri && q.ll && !shared_x) loglik_tri_pre(c, e, fm, Yf, &q);
     if (e.tri && shared_x) {              // (the wait for Q the skipped product would have queued; the log-likelihood's tail has passed it)
         if (e.wait_q) GP_HIP(hipStreamWaitEvent(s, c->ev_q[c->tgen], 0));
         e.wait_q = false;
@@ -455,21 +573,8 @@ static int predict_fold(gpcsd_ctx *c, const gpcsd_hparams *hp, EigState &e, cons
     c->tl("Pc end (s5)", c->stream5);
     if (e.tri) {
         // Bm~ = the solutions of the shifted tridiagonal systems (es[x'] m T_p + sig2 I) b = w, row by row of W~ = diag(U)^T Y~ Q
-        const char *const *tg = eigh_fold_tags(c, 1);
-        const double *d[2], *ee[2], *am[2];
-        int np[2], c0[2];
-        for (int p = 0; p < 2; ++p) {
-            np[p] = p ? nta : nts;
-            c0[p] = p ? nts : 0;
-            const EigArenaView av = eigh_arena_view(c, tg[p], np[p], e.tri_count);
-            const long o = (long)e.tri_rep * av.blk;
-            d[p] = av.d + o; ee[p] = av.e + o; am[p] = av.amax + o;
-        }
-        if (c->t1_wait_pending) {
-            GP_HIP(hipStreamWaitEvent(s, c->ev_t1, 0));
-            c->t1_wait_pending = false;
-        }
-        k_tridiag_solve(c, W, Bm, fm.fs.w, d, ee, am, e.d_sig, nx, R, nt, np, c0, s);
+        const TriOperands o = tri_operands(c, e, fm, s);
+        k_tridiag_solve(c, W, Bm, fm.fs.w, o.d, o.e, o.amax, e.d_sig, nx, R, nt, o.np, o.c0, s, /*pass=*/0, /*hint=*/q.solve_pass);
         GP_HIP(hipEventRecord(c->ev_tri_done[c->tgen], s));     // the last reader of Q / the tridiagonal on this stream
         c->tri_reader_queued[c->tgen] = true;
     } else {
@@ -477,9 +582,7 @@ static int predict_fold(gpcsd_ctx *c, const gpcsd_hparams *hp, EigState &e, cons
     }
     for (int which = 1; which <= 2; ++which) {
         if (!(type & which)) continue;
-        double *o_sum = c->buf<double>(which == 1 ? "pred_out_csd" : "pred_out_lfp", out_elems);
-        double *o_list = want_lists ? c->buf<double>(which == 1 ? "pred_out_csd_list" : "pred_out_lfp_list", out_elems * C)
-                                    : nullptr;
+        const PredOut out = pred_out_bufs(c, which, out_elems, C, want_lists);
         GemmDesc g5[2], g6[2];
         for (int p = 0; p < 2; ++p) {     // S~[p rows] = M1_p Bm~[p rows]
             const int np = p ? na : ns, nzp = p ? nza : nzs;
@@ -515,15 +618,15 @@ static int predict_fold(gpcsd_ctx *c, const gpcsd_hparams *hp, EigState &e, cons
             pu.ncolS = (long)nzs * R; pu.ncolA = (long)nza * R; pu.anti_row0 = (long)nzs * R;
             pu.R = R; pu.nt = nt; pu.C = C;
             pu.sz = sz; pu.st = fm.sym_t;
-            pu.list = o_list; pu.list_stride = (long)out_elems; pu.sum = o_sum;
-            if (!pred_unfold_chunked(c, pu, which - 1, nz, out_elems, want_lists, s)) gemm_pred_unfold(c, pu, s);
+            pu.list = out.list; pu.list_stride = (long)out_elems; pu.sum = out.sum;
+            if (!pred_unfold_chunked(c, q, pu, which - 1, out_elems, s)) gemm_pred_unfold(c, pu, s);
         } else {
             gemm_pair(c, g6[0], g6[1], s);
-            k_unfold_swap_sum(c, comp, C, o_list, (long)out_elems, o_sum, R, nt, sz, fm.sym_t, s, ntsP, ntaP, ldcomp);
+            k_unfold_swap_sum(c, comp, C, out.list, (long)out_elems, out.sum, R, nt, sz, fm.sym_t, s, ntsP, ntaP, ldcomp);
         }
     }
     c->tl("predict end (main)", s);
-    if (async && c->prof_mode != 1) {     // results stay on the device: return with the tail still in flight
+    if (q.async && c->prof_mode != 1) {   // results stay on the device: return with the tail still in flight
         c->async_pending = true;
         c->status_zeroed = false;
         return 0;
@@ -539,8 +642,11 @@ static int predict_fold(gpcsd_ctx *c, const gpcsd_hparams *hp, EigState &e, cons
 // the product instead of ~220 us.  Rows: orbit a writes z = rep_i[a] and rep_j[a] -- runs of consecutive rows are one copy each
 // (a mirror-symmetric probe gives two runs per chunk).  Returns false when it does not apply (the caller launches the product whole).
 // gpcsd_predict_chunked_copy(ctx, 0) / GPCSD_PRED_CHUNKED=0: A/B.
-static bool pred_unfold_chunked(gpcsd_ctx *c, PredUnfoldDesc pu, int which0, int nz, size_t out_elems, bool want_lists, hipStream_t s) {
-    gpcsd_ctx::PredSink &sk = c->pred_sink;
+static bool pred_unfold_chunked(gpcsd_ctx *c, const PredCall &q, PredUnfoldDesc pu, int which0, size_t out_elems, hipStream_t s) {
+    if (!q.sink) return false;
+    PredSink &sk = *q.sink;
+    const int nz = q.nz;
+    const bool want_lists = q.want_lists;
     if (!sk.active || !c->pred_chunked || !sk.sum[which0] || (want_lists && !sk.list[which0]) || c->prof_mode == 1) return false;
     const auto it = c->sym_host.find(pu.sz.rep_i);
     if (it == c->sym_host.end()) return false;
@@ -586,7 +692,7 @@ static bool pred_unfold_chunked(gpcsd_ctx *c, PredUnfoldDesc pu, int which0, int
         hipEvent_t ev = c->get_event();
         GP_HIP(hipEventRecord(ev, s));
         GP_HIP(hipStreamWaitEvent(sc, ev, 0));
-        c->pred_sink_events.push_back(ev);                        // (back to the pool once gpcsd_predict has synchronised)
+        sk.events.push_back(ev);                                  // (back to the pool once gpcsd_predict has synchronised)
         for (size_t i = 0; i < rows.size();) {
             size_t j = i + 1;
             while (j < rows.size() && rows[j] == rows[j - 1] + 1) ++j;
@@ -666,41 +772,19 @@ static PredFullFront predict_full_front(gpcsd_ctx *c, const gpcsd_hparams *hp, E
 // Posterior mean into ctx-owned device buffers, already in the reference's output layout (z, t, trial):
 //   pred_out_csd / pred_out_lfp            (nz, ntstar, R)
 //   pred_out_csd_list / pred_out_lfp_list  (C, nz, ntstar, R)     when want_lists
-static int predict_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar,
-                        int type, bool want_lists, bool async) {
-    GP_REQUIRE(z && tstar && nz > 0 && ntstar > 0, -3, "predict: bad arguments");
-    GP_REQUIRE(type >= 1 && type <= 3, -3, "predict: type must be CSD(1), LFP(2) or BOTH(3)");
-    GP_REQUIRE(c->nt > 0 && ntstar == c->nt, -22,
-               "predict: len(t)=%d must equal the training nt=%d (the reference's reshape raises ValueError, gpcsd1d.py:279)",
-               ntstar, c->nt);
-    GP_REQUIRE(c->d_lfp != nullptr, -4, "lfp not set (call gpcsd_set_lfp)");
-    // folded basis when the grids, the prediction sites and the prediction times all share the reflection symmetries
-    const FoldMode fm0 = fold_mode(c, hp);         // the decision only: views are taken after the front half
-    // a folded side needs its outputs on a grid with the same symmetry (t* = t; mirror-symmetric sites); an unfolded side
-    // takes any sites / times
-    const bool t_ok = fm0.on && ntstar == c->nt &&
-                      (!fm0.ft.on || ((int)c->time_host.size() == c->nt &&
-                                      memcmp(c->time_host.data(), tstar, (size_t)ntstar * sizeof(double)) == 0));
-    if (t_ok) {
-        SymDev sz = fm0.fs.on ? site_symmetry(c, z, nz, c->dim) : identity_sym(c, nz);
-        // sites without the electrodes' symmetry (the reference's own use: four off-grid depths): the spatial side unfolded, the
-        // temporal side folded as ever -- not the full-size path
-        bool fold_s = true;
-        if (!(sz.ns > 0 && sz.ns + sz.na == nz) && fm0.fs.on && fm0.ft.on) {
-            fold_s = false;
-            sz = identity_sym(c, nz);
-        }
-        if (sz.ns > 0 && sz.ns + sz.na == nz) {
-            // the chains go first (they need no upload of this call), then the host-side uploads
-            const bool ptri = fm0.ft.on && predict_tridiag_applies(fm0.ft.ns, fm0.ft.na, c->ntrials);
-            // no jitter in predict (gpcsd1d.py:258); X = Y~ Q goes through loglik_tri_pre: stage 5 may apply
-            EigState ef = front_half(c, hp, 0.0, false, /*join_s=*/false, /*want_tri=*/ptri, fold_s ? -1 : 1, /*x_via_tri_pre=*/ptri);
-            const FoldMode fm = fold_mode(c, hp, fold_s);
-            const double *Yf = folded_lfp(c, fm);
-            double *dzf = c->upload_cached<double>("pred_z", z, (size_t)nz * c->dim);
-            double *dtf = c->upload_cached<double>("pred_tstar", tstar, ntstar);
-            return predict_fold(c, hp, ef, fm, Yf, sz, dzf, nz, dtf, type, want_lists, async);
-        }
+static int predict_impl(gpcsd_ctx *c, const PredCall &q) {
+    check_predict_args(c, q);
+    const gpcsd_hparams *hp = q.hp;
+    const double *z = q.z, *tstar = q.tstar;
+    const int nz = q.nz, ntstar = q.ntstar, type = q.type;
+    const bool want_lists = q.want_lists;
+    PredPlan P = pred_plan(c, hp, z, nz, tstar, ntstar);
+    if (P.form != PredPlan::FULL) {
+        // the chains go first (they need no upload of this call), then the host-side uploads
+        // no jitter in predict (gpcsd1d.py:258); X = Y~ Q goes through loglik_tri_pre: stage 5 may apply
+        EigState ef = front_half(c, hp, 0.0, false, /*join_s=*/false, /*want_tri=*/P.tri, P.fold_s() ? -1 : 1, /*x_via_tri_pre=*/P.tri);
+        pred_operands(c, q, P, fold_mode(c, hp, P.fold_s()));
+        return predict_fold(c, q, P, ef);
     }
     EigState e = front_half(c, hp, 0.0);           // no jitter in predict (gpcsd1d.py:258)
     const int nx = c->nx, nt = c->nt, R = c->ntrials, C = hp->n_temporal;
@@ -716,9 +800,7 @@ static int predict_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, 
     const size_t out_elems = (size_t)nz * RT;
     for (int which = 1; which <= 2; ++which) {
         if (!(type & which)) continue;
-        double *o_sum = c->buf<double>(which == 1 ? "pred_out_csd" : "pred_out_lfp", out_elems);
-        double *o_list = want_lists ? c->buf<double>(which == 1 ? "pred_out_csd_list" : "pred_out_lfp_list", out_elems * C)
-                                    : nullptr;
+        const PredOut out = pred_out_bufs(c, which, out_elems, C, want_lists);
         GemmDesc g5;                      // S[z][(r,i')] = sum_x' M1[z][x'] Bm[x'][(r,i')]
         g5.M = nz; g5.N = (int)RT; g5.K = nx;
         g5.A = M1 + (size_t)(which - 1) * nz * nx; g5.lda = nx; g5.B = Bm; g5.ldb = RT; g5.C = S; g5.ldc = RT;
@@ -740,7 +822,7 @@ static int predict_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, 
         g6.A = S; g6.lda = nt; g6.B = Pc; g6.ldb = (long)C * nt; g6.C = comp; g6.ldc = (long)C * nt;
         g6.prof_name = "gemm_pred_tstar";
         gemm_f64(c, g6, s);
-        k_swap_last2_sum(c, comp, C, o_list, (long)out_elems, o_sum, nz, R, nt, s);     // (z,r,c,t) -> (c,z,t,r), sum over c
+        k_swap_last2_sum(c, comp, C, out.list, (long)out_elems, out.sum, nz, R, nt, s);     // (z,r,c,t) -> (c,z,t,r), sum over c
     }
     return finish_call(c, e, nullptr, 0);
 }
@@ -783,9 +865,8 @@ static void front_half_pair(gpcsd_ctx *c, const gpcsd_hparams *const hp[2], cons
     const double *t = (const double *)c->bufs["time_t"].p;
     // replicas of the temporal problem: ONE when the two sets have the same temporal hyper-parameters (every loglik -> predict
     // pair: the jitter is spatial) and either the decomposition cache or the pair's sharing of X says that equal sides are formed
-    // once -- the second replica would be the same launches on the same matrix, the same bits (GPCSD_PAIR_ONE_KT=0: A/B)
-    static const bool one_kt_off = getenv("GPCSD_PAIR_ONE_KT") && getenv("GPCSD_PAIR_ONE_KT")[0] == '0';
-    const int nT = (same_temporal(hp[0], hp[1]) && (c->decomp_cache_on || (c->pair_share_x && !one_kt_off))) ? 1 : 2;
+    // once -- the second replica would be the same launches on the same matrix, the same bits
+    const int nT = (same_temporal(hp[0], hp[1]) && (c->decomp_cache_on || c->pair_share_x)) ? 1 : 2;
     double *scal = c->buf<double>("scal_status", gpcsd_ctx::RESULT_DOUBLES);
     int *status = reinterpret_cast<int *>(scal + gpcsd_ctx::SCAL_N);
     const bool clear_now = !c->status_zeroed && !c->async_pending;
@@ -822,52 +903,43 @@ static void front_half_pair(gpcsd_ctx *c, const gpcsd_hparams *const hp[2], cons
     const int nS = share_s ? 1 : 2;
     out.share_s = share_s;
     if (share_s) ++c->pair_shared_s_calls;
-    auto run_S = [&]() {
-        c->tl("S chain start (s3)", s3);
-        const bool sfill = spatial_fill_applies(c, sym_s, nx);
-        if (sfill) {
-            // the fill folds Ks and adds each replica's jitter to the folded diagonals: one assembly, no copy, no diagonal pass
-            if (same_ks) build_kphi(c, g, hp[0]->R, hp[0]->eps, hp[0]->ell_s, nullptr, 0, 0.0, Ks, s3, "ks_");
-            else for (int b = 0; b < 2; ++b) build_kphi(c, g, hp[b]->R, hp[b]->eps, hp[b]->ell_s, nullptr, 0, 0.0, Ks + b * nxx, s3, "ks_");
-            spatial_fill(c, Ks, nx, same_ks ? 0 : nxx, nS, jitter, *sym_s, status, 2, s3);
-        } else if (share_s) {
-            build_kphi(c, g, hp[0]->R, hp[0]->eps, hp[0]->ell_s, nullptr, 0, jitter[0], Ks, s3, "ks_");
-        } else if (same_ks) {
-            const int lo = jitter[0] == 0.0 ? 0 : 1, hi = 1 - lo;           // assemble the one without a shift (if any) first
-            build_kphi(c, g, hp[lo]->R, hp[lo]->eps, hp[lo]->ell_s, nullptr, 0, 0.0, Ks + lo * nxx, s3, "ks_");
-            GP_HIP(hipMemcpyAsync(Ks + hi * nxx, Ks + lo * nxx, (size_t)nxx * sizeof(double), hipMemcpyDeviceToDevice, s3));
-            if (jitter[lo] != 0.0) k_add_diag(c, Ks + lo * nxx, nx, jitter[lo], s3);
-            if (jitter[hi] != 0.0) k_add_diag(c, Ks + hi * nxx, nx, jitter[hi], s3);
-        } else {
-            for (int b = 0; b < 2; ++b) build_kphi(c, g, hp[b]->R, hp[b]->eps, hp[b]->ell_s, nullptr, 0, jitter[b], Ks + b * nxx, s3, "ks_");
-        }
-        // two replicas of the spatial problem on stream3 (status words [0], [2]) -- or the one both sets share
-        {
-            ProfScope ps(c, "eigh_spatial", 9.0 * (double)nx * nx * nx * nS, s3);
-            EighCall r;
-            r.side[0] = {Ks, nx, es, Qs, sym_s, nS, /*prefolded=*/sfill};
-            r.status = status; r.status_stride = 2;
-            r.need_merged = !fold_s;
-            eigh_pair_device(c, r, s3);
-        }
-        if (share_s) {                   // set 1's spectrum: set 0's shifted by the difference of the jitters, in replica 1's slots
-            const double dj = jitter[1] - jitter[0];
-            if (vs.on) k_shift_copy(c, vs.w, vs.w + vs.sw, nx, dj, s3);
-            if (!vs.on || !fold_s) k_shift_copy(c, es, es + nx, nx, dj, s3);
-        }
-        GP_HIP(hipEventRecord(c->ev_sjoin, s3));
-        c->tl("S chain end (s3)", s3);
-    };
     // The temporal chain's long first kernels go first; staged, the host queues the spatial chain (~0.1 ms of launches) before
     // it comes back for the temporal chain's second stage -- stage 1 runs half a millisecond, the queue is never empty
-    static const bool s_first = getenv("GPCSD_S_FIRST") && getenv("GPCSD_S_FIRST")[0] == '1';     // (A/B: the spatial chain queued first)
-    if (s_first) {
-        run_S();
-        tchain_begin(c, tc, build_kts);
+    tchain_begin(c, tc, build_kts);
+    c->tl("S chain start (s3)", s3);
+    const bool sfill = spatial_fill_applies(c, sym_s, nx);
+    if (sfill) {
+        // the fill folds Ks and adds each replica's jitter to the folded diagonals: one assembly, no copy, no diagonal pass
+        if (same_ks) build_kphi(c, g, hp[0]->R, hp[0]->eps, hp[0]->ell_s, nullptr, 0, 0.0, Ks, s3, "ks_");
+        else for (int b = 0; b < 2; ++b) build_kphi(c, g, hp[b]->R, hp[b]->eps, hp[b]->ell_s, nullptr, 0, 0.0, Ks + b * nxx, s3, "ks_");
+        spatial_fill(c, Ks, nx, same_ks ? 0 : nxx, nS, jitter, *sym_s, status, 2, s3);
+    } else if (share_s) {
+        build_kphi(c, g, hp[0]->R, hp[0]->eps, hp[0]->ell_s, nullptr, 0, jitter[0], Ks, s3, "ks_");
+    } else if (same_ks) {
+        const int lo = jitter[0] == 0.0 ? 0 : 1, hi = 1 - lo;           // assemble the one without a shift (if any) first
+        build_kphi(c, g, hp[lo]->R, hp[lo]->eps, hp[lo]->ell_s, nullptr, 0, 0.0, Ks + lo * nxx, s3, "ks_");
+        GP_HIP(hipMemcpyAsync(Ks + hi * nxx, Ks + lo * nxx, (size_t)nxx * sizeof(double), hipMemcpyDeviceToDevice, s3));
+        if (jitter[lo] != 0.0) k_add_diag(c, Ks + lo * nxx, nx, jitter[lo], s3);
+        if (jitter[hi] != 0.0) k_add_diag(c, Ks + hi * nxx, nx, jitter[hi], s3);
     } else {
-        tchain_begin(c, tc, build_kts);
-        run_S();
+        for (int b = 0; b < 2; ++b) build_kphi(c, g, hp[b]->R, hp[b]->eps, hp[b]->ell_s, nullptr, 0, jitter[b], Ks + b * nxx, s3, "ks_");
     }
+    // two replicas of the spatial problem on stream3 (status words [0], [2]) -- or the one both sets share
+    {
+        ProfScope ps(c, "eigh_spatial", 9.0 * (double)nx * nx * nx * nS, s3);
+        EighCall r;
+        r.side[0] = {Ks, nx, es, Qs, sym_s, nS, /*prefolded=*/sfill};
+        r.status = status; r.status_stride = 2;
+        r.need_merged = !fold_s;
+        eigh_pair_device(c, r, s3);
+    }
+    if (share_s) {                   // set 1's spectrum: set 0's shifted by the difference of the jitters, in replica 1's slots
+        const double dj = jitter[1] - jitter[0];
+        if (vs.on) k_shift_copy(c, vs.w, vs.w + vs.sw, nx, dj, s3);
+        if (!vs.on || !fold_s) k_shift_copy(c, es, es + nx, nx, dj, s3);
+    }
+    GP_HIP(hipEventRecord(c->ev_sjoin, s3));
+    c->tl("S chain end (s3)", s3);
     tchain_finish(c, tc);
     c->decomp_gen[0] = c->decomp_gen[1] = -1;          // replicas are not what the separate calls' cache looks for
     const double *d_sig[2] = {c->upload_cached<double>("sig2n", hp[0]->sig2n, 1), c->upload_cached<double>("sig2n_pair", hp[1]->sig2n, 1)};
@@ -903,10 +975,7 @@ static int drain_async(gpcsd_ctx *c) {
     GP_HIP(hipStreamSynchronize(c->stream2));
     GP_HIP(hipStreamSynchronize(c->stream3));
     int rc = finish_status(c, st, gpcsd_ctx::STATUS_N);        // downloads + synchronises; the words are cleared by the next call's front half
-    if (c->last_pred.have && q_pipe_missed(c, rc, c->last_pred.piped)) {      // (see q_pipe_missed: the queued prediction again)
-        const gpcsd_ctx::PredKeep &k = c->last_pred;
-        rc = predict_impl(c, &k.hp.hp, k.z.data(), k.nz, k.ts.data(), k.nts, k.type, k.lists, false);
-    }
+    if (c->last_pred.have) replay_if_missed(c, rc, c->last_pred.piped, nullptr, nullptr, &c->last_pred.call);     // the queued prediction
     return rc;
 }
 
@@ -914,47 +983,24 @@ extern "C" int gpcsd_predict_resident(gpcsd_ctx *c, const gpcsd_hparams *hp, con
                                       int ntstar, int type, int want_lists) {
     GP_API_BEGIN(c)
     const bool piped = c->q_pipe;
-    const int rc = predict_impl(c, hp, z, nz, tstar, ntstar, type, want_lists != 0, /*async=*/true);
-    if (rc == 0) keep_prediction(c, piped, hp, z, nz, tstar, ntstar, type, want_lists != 0);
+    const PredCall q = pred_call(hp, z, nz, tstar, ntstar, type, want_lists != 0, /*async=*/true);
+    const int rc = predict_impl(c, q);
+    if (rc == 0) keep_prediction(c, piped, q);
     return rc;
     GP_API_END(c)
 }
 
-// What a paired call decides before it queues anything: does the paired front half apply, and in which form.
-struct PairPlan {
-    bool pair = false, fold_s = true, pred_tri = false;
-    FoldMode fm0;
-    SymDev sz;
-};
-static PairPlan pair_plan(gpcsd_ctx *c, const gpcsd_hparams *hp_ll, const gpcsd_hparams *hp_pr, const double *z, int nz, const double *tstar,
+// What a paired call decides before it queues anything: the prediction's plan, which both sets take -- or FULL where the paired front
+// half does not apply (it serves the folded-basis tails only): the call is then the two calls one after the other.
+static PredPlan pair_plan(gpcsd_ctx *c, const gpcsd_hparams *hp_ll, const gpcsd_hparams *hp_pr, const double *z, int nz, const double *tstar,
                           int ntstar) {
-    PairPlan P;
-    // the paired front half serves the folded-basis tails only; anything else is the two calls one after the other
-    bool pair = two_stream_front() && c->prof_mode != 1 && !uses_host_kt(hp_ll) && !uses_host_kt(hp_pr) &&
-                hp_ll->n_sig2n == 1 && hp_pr->n_sig2n == 1;
-    if (pair) {
-        P.fm0 = fold_mode(c, hp_ll);
-        pair = P.fm0.on && fold_mode(c, hp_pr).on &&
-               (!P.fm0.ft.on || ((int)c->time_host.size() == c->nt &&
-                                 memcmp(c->time_host.data(), tstar, (size_t)ntstar * sizeof(double)) == 0));
-    }
-    if (pair) {
-        P.sz = P.fm0.fs.on ? site_symmetry(c, z, nz, c->dim) : identity_sym(c, nz);
-        if (!(P.sz.ns > 0 && P.sz.ns + P.sz.na == nz) && P.fm0.fs.on && P.fm0.ft.on) {    // sites without the electrodes' symmetry: spatial
-            P.fold_s = false;                                                                // side unfolded for BOTH sets (see predict_impl)
-            P.sz = identity_sym(c, nz);
-            P.fm0 = fold_mode(c, hp_ll, false);
-        }
-        pair = P.sz.ns > 0 && P.sz.ns + P.sz.na == nz;
-    }
-    P.pair = pair;
-    // (decided here, where the fold sizes are known: does the prediction take the tridiagonal form too?)
-    if (pair) P.pred_tri = P.fm0.ft.on && predict_tridiag_applies(P.fm0.ft.ns, P.fm0.ft.na, c->ntrials);
-    return P;
+    const bool may = two_stream_front() && c->prof_mode != 1 && !uses_host_kt(hp_ll) && !uses_host_kt(hp_pr) && hp_ll->n_sig2n == 1 &&
+                     hp_pr->n_sig2n == 1 && fold_mode(c, hp_ll).on;
+    return may ? pred_plan(c, hp_pr, z, nz, tstar, ntstar) : PredPlan();
 }
 
 // Everything the paired front half's launches depend on (a prefetched front half is only taken by a call with the same key)
-static std::vector<unsigned char> pair_key(const gpcsd_ctx *c, const gpcsd_hparams *const hp[2], const double jit[2], const PairPlan &P) {
+static std::vector<unsigned char> pair_key(const gpcsd_ctx *c, const gpcsd_hparams *const hp[2], const double jit[2], const PredPlan &P) {
     std::vector<double> k;
     for (int b = 0; b < 2; ++b) {
         const gpcsd_hparams *h = hp[b];
@@ -962,7 +1008,7 @@ static std::vector<unsigned char> pair_key(const gpcsd_ctx *c, const gpcsd_hpara
         k.push_back((double)h->n_temporal); k.push_back((double)h->n_sig2n); k.push_back(h->sig2n[0]);
         for (int i = 0; i < h->n_temporal; ++i) { k.push_back((double)h->kind[i]); k.push_back(h->ell_t[i]); k.push_back(h->sigma2_t[i]); }
     }
-    const double cfg[] = {(double)P.pred_tri, (double)P.fold_s, (double)c->grid_epoch, (double)c->alloc_epoch, (double)c->ntrials, (double)c->nx,
+    const double cfg[] = {(double)P.tri, (double)P.fold_s(), (double)c->grid_epoch, (double)c->alloc_epoch, (double)c->ntrials, (double)c->nx,
                           (double)c->nt, (double)c->q_pipe, (double)c->pair_share_s, (double)c->tail_early_exit,
                           (double)c->ll_tridiag_mode, (double)c->gram_fp32, (double)c->decomp_cache_on, (double)c->fold_gemm_on};
     k.insert(k.end(), cfg, cfg + sizeof(cfg) / sizeof(cfg[0]));
@@ -991,8 +1037,8 @@ extern "C" int gpcsd_prefetch_pair(gpcsd_ctx *c, const gpcsd_hparams *hp_ll, con
     GP_REQUIRE(hp_ll && hp_pr && z && tstar && nz > 0 && ntstar > 0, -3, "prefetch_pair: bad arguments");
     GP_REQUIRE(c->d_lfp != nullptr && c->nt > 0 && ntstar == c->nt, -4, "prefetch_pair: resident data / time grid do not match");
     pair_prefetch_drop(c);
-    const PairPlan P = pair_plan(c, hp_ll, hp_pr, z, nz, tstar, ntstar);
-    if (!P.pair || c->time_nt != c->nt || resident_geo(c).nx != c->nx) return 0;
+    const PredPlan P = pair_plan(c, hp_ll, hp_pr, z, nz, tstar, ntstar);
+    if (P.form == PredPlan::FULL || c->time_nt != c->nt || resident_geo(c).nx != c->nx) return 0;
     check_hp(c, hp_ll, c->nx);
     check_hp(c, hp_pr, c->nx);
     const gpcsd_hparams *hps[2] = {hp_ll, hp_pr};
@@ -1000,7 +1046,7 @@ extern "C" int gpcsd_prefetch_pair(gpcsd_ctx *c, const gpcsd_hparams *hp_ll, con
     PairPrefetch *pp = new PairPrefetch();
     try {
         // (not pipelined: the chain has a whole step's head start, T and Q follow it at once -- the same kernels, the same bits)
-        front_half_pair(c, hps, jit, pp->pf, P.pred_tri, /*x_via_tri_pre=*/false, P.fold_s);
+        front_half_pair(c, hps, jit, pp->pf, P.tri, /*x_via_tri_pre=*/false, P.fold_s());
     } catch (...) {
         delete pp;
         throw;
@@ -1027,38 +1073,31 @@ extern "C" int gpcsd_loglik_predict_async(gpcsd_ctx *c, const gpcsd_hparams *hp_
                                     "gpcsd_loglik_parts_wait)"});
     GP_API_BEGIN(c)
     GP_REQUIRE(hp_ll && hp_pr, -3, "loglik_predict_async: null hparams");
-    GP_REQUIRE(z && tstar && nz > 0 && ntstar > 0, -3, "predict: bad arguments");
-    GP_REQUIRE(type >= 1 && type <= 3, -3, "predict: type must be CSD(1), LFP(2) or BOTH(3)");
-    GP_REQUIRE(c->nt > 0 && ntstar == c->nt, -22,
-               "predict: len(t)=%d must equal the training nt=%d (the reference's reshape raises ValueError, gpcsd1d.py:279)",
-               ntstar, c->nt);
-    GP_REQUIRE(c->d_lfp != nullptr, -4, "lfp not set (call gpcsd_set_lfp)");
-    const PairPlan P = pair_plan(c, hp_ll, hp_pr, z, nz, tstar, ntstar);
-    const bool pair = P.pair;
-    const bool fold_s = P.fold_s;
-    const SymDev sz = P.sz;
-    {   // what gpcsd_loglik_parts_wait needs to evaluate the pair again (q_pipe_missed)
+    PredCall q = pred_call(hp_pr, z, nz, tstar, ntstar, type, want_lists != 0, /*async=*/true);
+    check_predict_args(c, q);
+    check_hp(c, hp_ll, c->nx);            // both sets, before anything of them is copied into the slot or into last_pred
+    check_hp(c, hp_pr, c->nx);
+    PredPlan P = pair_plan(c, hp_ll, hp_pr, z, nz, tstar, ntstar);
+    const bool pair = P.form != PredPlan::FULL;
+    if (pair) {
+        GP_REQUIRE(c->time_nt == c->nt, -4, "time grid has %d points but lfp has nt=%d", c->time_nt, c->nt);
+        GP_REQUIRE(resident_geo(c).nx == c->nx, -4, "geometry has %d electrodes but lfp has nx=%d", resident_geo(c).nx, c->nx);
+    }
+    {   // what gpcsd_loglik_parts_wait needs to evaluate the pair again (replay_if_missed)
         gpcsd_ctx::LlSlot &sl = c->ll_slot[(c->ll_head + c->ll_count) % gpcsd_ctx::LL_SLOTS];
         sl.piped = c->q_pipe;
         sl.hp.set(hp_ll);
-        keep_prediction(c, sl.piped, hp_pr, z, nz, tstar, ntstar, type, want_lists != 0);
+        keep_prediction(c, sl.piped, q);
         sl.pred_seq = c->pred_seq;
     }
     if (!pair) {
         const int rc = loglik_parts_impl(c, hp_ll, nullptr, true);
         if (rc != 0) return rc;
-        return predict_impl(c, hp_pr, z, nz, tstar, ntstar, type, want_lists != 0, true);
+        return predict_impl(c, q);
     }
-    GP_REQUIRE(c->time_nt == c->nt, -4, "time grid has %d points but lfp has nt=%d", c->time_nt, c->nt);
-    GP_REQUIRE(resident_geo(c).nx == c->nx, -4, "geometry has %d electrodes but lfp has nx=%d", resident_geo(c).nx, c->nx);
-    check_hp(c, hp_ll, c->nx);
-    check_hp(c, hp_pr, c->nx);
     const gpcsd_hparams *hps[2] = {hp_ll, hp_pr};
     const double jit[2] = {hp_ll->jitter, 0.0};          // no jitter in predict (gpcsd1d.py:258)
     PairFront pf;
-    const bool pred_tri = P.pred_tri;
-    (void)pred_tri;
-    (void)fold_s;
     // the front half: prefetched by the previous call's gpcsd_prefetch_pair (same arguments, nothing in between), or queued now
     bool taken = false;
     if (PairPrefetch *pp = static_cast<PairPrefetch *>(c->pair_prefetch)) {
@@ -1070,44 +1109,25 @@ extern "C" int gpcsd_loglik_predict_async(gpcsd_ctx *c, const gpcsd_hparams *hp_
         }
         pair_prefetch_drop(c);
     }
-    if (!taken) front_half_pair(c, hps, jit, pf, P.pred_tri, /*x_via_tri_pre=*/P.fm0.ft.on, P.fold_s);
-    const double *Yf = folded_lfp(c, pf.fm[1]);
-    const long up0 = c->upload_count;
-    double *dzf = c->upload_cached<double>("pred_z", z, (size_t)nz * c->dim);
-    double *dtf = c->upload_cached<double>("pred_tstar", tstar, ntstar);
-    // (sites or times uploaded just now, on the main stream: the builders that read them stay there)
-    // GPCSD_PRELUDE_SIDE: 0 never, 1 (default) when stage 5 is pipelined, 2 always, 3 also for announced pairs
-    static const int side_mode = getenv("GPCSD_PRELUDE_SIDE") ? atoi(getenv("GPCSD_PRELUDE_SIDE")) : 1;
-    const bool prelude_side = side_mode != 0 && c->upload_count == up0 &&
-                              (pf.e[0].pipe_pending || side_mode == 2 || (side_mode == 3 && taken));
-    const std::function<void()> ll_pre = [&]() {
-        if (pf.e[0].tri) loglik_tri_pre(c, pf.e[0], pf.fm[0], Yf);
-    };
-    const std::function<void()> ll_tail = [&]() {
-        double *Wll = c->buf<double>("proj_W_ll", (size_t)c->nx * c->ntrials * c->nt);
-        bool batched = true;
-        bool wrote = false;
-        if (pf.e[0].tri) wrote = loglik_tri_tail(c, pf.e[0], pf.fm[0], Yf, Wll, next_ll_slot(c));
-        else batched = loglik_fold_tail(c, pf.e[0], pf.fm[0], Yf, Wll);
-        (void)finish_loglik_async(c, pf.e[0], !batched, wrote);
-    };
+    if (!taken) front_half_pair(c, hps, jit, pf, P.tri, /*x_via_tri_pre=*/P.fm.ft.on, P.fold_s());
+    const bool uploaded = pred_operands(c, q, P, pf.fm[1]);
+    // what needs no decomposition goes to stream5 exactly when stage 5 is pending (the main stream has the log-likelihood's products
+    // to queue first) and nothing was uploaded just now on the main stream (the builders that read sites or times then stay there)
+    q.prelude_side = !uploaded && pf.e[0].pipe_pending;
+    PairLl ll{&pf.e[0], &pf.fm[0], false, false};
     // equal temporal hyper-parameters (every loglik -> predict pair of a fit or a bench step: the jitter is spatial): the prediction
     // reads the log-likelihood's X = Y~ Q instead of forming its own from the bit-identical second replica
     // (gpcsd_pair_share_x(ctx, 0, ..) / GPCSD_PAIR_SHARE_X=0: A/B)
-    const bool share_x = c->pair_share_x && pf.e[0].tri && pf.e[1].tri && ll_order() == 0 && same_temporal(hp_ll, hp_pr);
-    if (share_x) ++c->pair_shared_x_calls;
+    ll.share_x = c->pair_share_x && pf.e[0].tri && pf.e[1].tri && same_temporal(hp_ll, hp_pr);
+    if (ll.share_x) ++c->pair_shared_x_calls;
     // one spatial decomposition (PairFront::share_s): the two projected data sets W~ = diag(U)^T (Y~ Q or Y~) are then the same
     // product whenever both sets take the same form -- tridiagonal with X shared, or both with the temporal eigenvectors
-    const bool share_w = pf.share_s && (share_x || (!pf.e[0].tri && !pf.e[1].tri));
+    ll.share_w = pf.share_s && (ll.share_x || (!pf.e[0].tri && !pf.e[1].tri));
+    q.ll = &ll;
     // a pair that queued its own front half is (in a loop) followed by one that does the same while this one's solve runs: the
     // narrow form of the solve leaves room beside it (gram.hip: k_tridiag_solve)
-    struct SolvePass {
-        gpcsd_ctx *c;
-        SolvePass(gpcsd_ctx *cc, int v) : c(cc) { c->solve_pass = v; }
-        ~SolvePass() { c->solve_pass = 0; }
-    } solve_pass(c, taken ? 64 : 32);
-    return predict_fold(c, hp_pr, pf.e[1], pf.fm[1], Yf, sz, dzf, nz, dtf, type, want_lists != 0, true, &ll_tail, &ll_pre,
-                        share_x ? "ll_X" : nullptr, prelude_side, share_w ? "proj_W_ll" : nullptr);
+    q.solve_pass = taken ? 64 : 32;
+    return predict_fold(c, q, P, pf.e[1]);
     GP_API_END(c)
 }
 
@@ -1147,52 +1167,24 @@ extern "C" int gpcsd_device_buffer(gpcsd_ctx *c, const char *name, unsigned long
 extern "C" int gpcsd_predict(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar,
                              int type, double *csd_list, double *csd, double *lfp_list, double *lfp) {
     GP_API_BEGIN(c)
-    const bool want_lists = (csd_list != nullptr) || (lfp_list != nullptr);
     // the caller's arrays are known to the tail: a folded prediction copies its outputs out chunk by chunk under its last product
-    gpcsd_ctx::PredSink &sk = c->pred_sink;
-    sk = gpcsd_ctx::PredSink();
     // (... into page-locked arrays only -- the class API's come from its pinned pool.  Pageable arrays of another caller are
     // filled through the context's bounce blocks after the product: the runtime never gets to register the caller's pages,
     // ctx.hpp copy_in / copy_out)
+    PredSink sk;
+    sk.owner = c;
     sk.active = true;
     for (const double *p : {csd, csd_list, lfp, lfp_list})
         if (p && !gpcsd_ctx::host_is_pinned(p)) sk.active = false;
     sk.sum[0] = csd; sk.list[0] = csd_list; sk.sum[1] = lfp; sk.list[1] = lfp_list;
-    int rc;
-    try {
-        const bool piped = c->q_pipe;
-        rc = predict_impl(c, hp, z, nz, tstar, ntstar, type, want_lists, false);
-        if (q_pipe_missed(c, rc, piped)) {         // (a scheduling miss of the pipelined stage 5: again, unpipelined)
-            (void)hipStreamSynchronize(c->stream4);
-            for (hipEvent_t ev : c->pred_sink_events) c->event_pool.push_back(ev);
-            c->pred_sink_events.clear();
-            sk.done[0] = sk.done[1] = false;
-            rc = predict_impl(c, hp, z, nz, tstar, ntstar, type, want_lists, false);
-        }
-    } catch (...) {
-        sk.active = false;
-        (void)hipStreamSynchronize(c->stream4);
-        throw;
-    }
-    sk.active = false;
-    if (rc < 0) {
-        (void)hipStreamSynchronize(c->stream4);
-        return rc;
-    }
-    const size_t out_elems = (size_t)nz * ntstar * c->ntrials;
-    const int C = hp->n_temporal;
-    if ((type & 1) && !sk.done[0]) {
-        if (csd) c->download(csd, c->bufs["pred_out_csd"].p, out_elems * sizeof(double));
-        if (csd_list) c->download(csd_list, c->bufs["pred_out_csd_list"].p, out_elems * C * sizeof(double));
-    }
-    if ((type & 2) && !sk.done[1]) {
-        if (lfp) c->download(lfp, c->bufs["pred_out_lfp"].p, out_elems * sizeof(double));
-        if (lfp_list) c->download(lfp_list, c->bufs["pred_out_lfp_list"].p, out_elems * C * sizeof(double));
-    }
-    if (sk.done[0] || sk.done[1]) GP_HIP(hipStreamSynchronize(c->stream4));
+    PredCall q = pred_call(hp, z, nz, tstar, ntstar, type, csd_list != nullptr || lfp_list != nullptr, /*async=*/false);
+    q.sink = &sk;
+    const bool piped = c->q_pipe;
+    int rc = predict_impl(c, q);
+    replay_if_missed(c, rc, piped, nullptr, nullptr, &q);
+    if (rc < 0) return rc;
+    pred_download(c, q, sk);
     c->sync();
-    for (hipEvent_t ev : c->pred_sink_events) c->event_pool.push_back(ev);
-    c->pred_sink_events.clear();
     return rc;
     GP_API_END(c)
 }
@@ -1202,8 +1194,11 @@ extern "C" int gpcsd_predict(gpcsd_ctx *c, const gpcsd_hparams *hp, const double
 //   P_c[i'][j] = sum_i Qt[i][i'] k_c(t*_j, t_i),      out_c[z][j][r] = sum_i' S[(z, r)][i'] P_c[i'][j],
 // and the last product writes the output layout itself (gemm_pred_at).  Both sides unfolded: a window of t has no mirror symmetry.
 // Outputs: the buffers of predict_impl, (nz, ntstar, R) / (C, nz, ntstar, R).
-static int predict_at_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar,
-                           int type, bool want_lists) {
+static int predict_at_impl(gpcsd_ctx *c, const PredCall &q) {
+    const gpcsd_hparams *hp = q.hp;
+    const double *z = q.z, *tstar = q.tstar;
+    const int nz = q.nz, ntstar = q.ntstar, type = q.type;
+    const bool want_lists = q.want_lists;
     GP_REQUIRE(z && tstar && nz > 0 && ntstar > 0, -3, "predict_at: bad arguments");
     GP_REQUIRE(type >= 1 && type <= 3, -3, "predict_at: type must be CSD(1), LFP(2) or BOTH(3)");
     GP_REQUIRE(hp != nullptr, -3, "null hparams");
@@ -1232,9 +1227,7 @@ static int predict_at_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *
     }
     for (int which = 1; which <= 2; ++which) {
         if (!(type & which)) continue;
-        double *o_sum = c->buf<double>(which == 1 ? "pred_out_csd" : "pred_out_lfp", out_elems);
-        double *o_list = want_lists ? c->buf<double>(which == 1 ? "pred_out_csd_list" : "pred_out_lfp_list", out_elems * C)
-                                    : nullptr;
+        const PredOut out = pred_out_bufs(c, which, out_elems, C, want_lists);
         GemmDesc g5;                      // S[z][(r,i')] = sum_x' M1[z][x'] Bm[x'][(r,i')]
         g5.M = nz; g5.N = (int)RT; g5.K = nx;
         g5.A = M1 + (size_t)(which - 1) * nz * nx; g5.lda = nx; g5.B = Bm; g5.ldb = RT; g5.C = S; g5.ldc = RT;
@@ -1243,7 +1236,7 @@ static int predict_at_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *
         PredAtDesc pa;                    // out[cc][z][j][r] = sum_i' Pcat[i'][cc*ntstar + j] S[(z,r)][i'], and the sum over cc
         pa.S = S; pa.lds = nt; pa.Pc = Pc; pa.ldp = (long)C * ntstar;
         pa.K = nt; pa.nts = ntstar; pa.C = C; pa.R = R; pa.ncol = (long)nz * R;
-        pa.list = o_list; pa.list_stride = (long)out_elems; pa.sum = o_sum;
+        pa.list = out.list; pa.list_stride = (long)out_elems; pa.sum = out.sum;
         gemm_pred_at(c, pa, s);
     }
     // the resident outputs are this call's now: nothing queued earlier may be evaluated again over them (drain_async, the paired wait)
@@ -1255,25 +1248,19 @@ static int predict_at_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *
 extern "C" int gpcsd_predict_at_resident(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar,
                                          int ntstar, int type, int want_lists) {
     GP_API_BEGIN(c)
-    return predict_at_impl(c, hp, z, nz, tstar, ntstar, type, want_lists != 0);
+    return predict_at_impl(c, pred_call(hp, z, nz, tstar, ntstar, type, want_lists != 0, false));
     GP_API_END(c)
 }
 
 extern "C" int gpcsd_predict_at(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar,
                                 int type, double *csd_list, double *csd, double *lfp_list, double *lfp) {
     GP_API_BEGIN(c)
-    const int rc = predict_at_impl(c, hp, z, nz, tstar, ntstar, type, csd_list != nullptr || lfp_list != nullptr);
+    const PredCall q = pred_call(hp, z, nz, tstar, ntstar, type, csd_list != nullptr || lfp_list != nullptr, false);
+    const int rc = predict_at_impl(c, q);
     if (rc < 0) return rc;
-    const size_t out_elems = (size_t)nz * ntstar * c->ntrials;
-    const int C = hp->n_temporal;
-    if (type & 1) {
-        if (csd) c->download(csd, c->bufs["pred_out_csd"].p, out_elems * sizeof(double));
-        if (csd_list) c->download(csd_list, c->bufs["pred_out_csd_list"].p, out_elems * C * sizeof(double));
-    }
-    if (type & 2) {
-        if (lfp) c->download(lfp, c->bufs["pred_out_lfp"].p, out_elems * sizeof(double));
-        if (lfp_list) c->download(lfp_list, c->bufs["pred_out_lfp_list"].p, out_elems * C * sizeof(double));
-    }
+    PredSink out;
+    out.sum[0] = csd; out.list[0] = csd_list; out.sum[1] = lfp; out.list[1] = lfp_list;
+    pred_download(c, q, out);
     c->sync();
     return rc;
     GP_API_END(c)

@@ -77,6 +77,22 @@ struct PerDeviceOnce {
 };
 }  // namespace gpcsd
 
+// A prediction's request (capi_fused.inl): everything a prediction is told travels in it, as a solve's does in EighCall -- nothing
+// is set on the context around the call.
+struct PredSink;                            // gpcsd_predict's host outputs
+struct PairLl;                              // the paired call's log-likelihood
+struct PredCall {
+    const gpcsd_hparams *hp = nullptr;
+    const double *z = nullptr, *tstar = nullptr;
+    int nz = 0, ntstar = 0, type = 0;
+    bool want_lists = false, async = false;
+    PredSink *sink = nullptr;               // gpcsd_predict: the caller's arrays, filled chunk by chunk under the last product
+    int solve_pass = 0;                     // trials per pass of the tridiagonal solve: 0 by size, 32 the two-per-CU form, 64 the one-pass
+                                            // form (gram.hip: k_tridiag_solve)
+    PairLl *ll = nullptr;                   // gpcsd_loglik_predict_async: the log-likelihood whose products this call queues with its own
+    bool prelude_side = false;              // ... and what needs no decomposition goes to stream5
+};
+
 struct gpcsd_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -125,11 +141,11 @@ struct gpcsd_ctx {
             hp.sig2n = sig.data();
         }
     };
-    struct PredKeep {
-        bool have = false, piped = false, lists = false;
+    struct PredKeep {                       // a PredCall with owned copies of hp, z and tstar (capi_fused.inl: keep_prediction)
+        bool have = false, piped = false;
+        PredCall call;
         HpKeep hp;
         std::vector<double> z, ts;
-        int nz = 0, nts = 0, type = 0;
     };
     struct LlSlot {
         hipEvent_t ev = nullptr;
@@ -244,15 +260,6 @@ struct gpcsd_ctx {
     bool m1_read_queued = false;
     int q_pipe_mask = -1;                   // stage 5: bit p set = the product on Q's finished columns is launched behind panel p
                                             // (always behind the last; a skipped panel's columns ride in the next launch); -1: default
-    // gpcsd_predict (host outputs): the caller's arrays while the call runs.  The fused last product of a folded prediction is then
-    // launched in chunks of site orbits and every chunk's finished output rows are copied out (stream4: the DMA engine) while the
-    // next chunk computes -- predict_sink_done[which] tells gpcsd_predict that nothing is left to download (capi_fused.inl).
-    struct PredSink {
-        bool active = false;
-        double *sum[2] = {nullptr, nullptr}, *list[2] = {nullptr, nullptr};       // [0] csd, [1] lfp
-        bool done[2] = {false, false};
-    } pred_sink;
-    std::vector<hipEvent_t> pred_sink_events;
     bool pred_chunked = true;               // gpcsd_predict_chunked_copy() / GPCSD_PRED_CHUNKED=0
     long pred_chunked_calls = 0;
     std::map<const int *, std::vector<int>> sym_host;       // host copies (rep_i | rep_j) of the orbit tables, by device pointer
@@ -264,7 +271,6 @@ struct gpcsd_ctx {
     // product less per cfg3 step, but the step measured 6-10 % SLOWER (the prediction's LDS-filling solve then starts 70 us earlier and
     // lands on the next step's spatial Gram assembly: DESIGN 4.13), and the pair no longer has the bits of its fenced calls.
     bool pair_share_s = false;
-    int solve_pass = 0;                     // trials per pass of the next tridiagonal solve: 0 / 64 the one-pass form, 32 the two-per-CU form (gram.hip: k_tridiag_solve)
     long pair_shared_s_calls = 0;
     long pair_shared_x_calls = 0;           // paired calls whose prediction read the log-likelihood's X = Y~ Q (capi_fused.inl)
     // Decomposition cache (capi.hip::front_half): predict() right after loglik() / fit() with the same hyper-parameters

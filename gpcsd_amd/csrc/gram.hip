@@ -971,7 +971,7 @@ int k_tridiag_solve_pass(int npmax, int R) {
 
 void k_tridiag_solve(gpcsd_ctx *c, const double *W, double *B, const double *es, const double *const d[2], const double *const e[2],
                      const double *const amax[2], const double *sig, int nx, int R, int nt, const int np[2], const int c0[2],
-                     hipStream_t s, int pass) {
+                     hipStream_t s, int pass, int hint) {
     TriSolveArgs g{};
     g.W = W; g.B = B; g.es = es; g.sig = sig; g.nx = nx; g.R = R; g.nt = nt;
     for (int p = 0; p < 2; ++p) {
@@ -983,13 +983,13 @@ void k_tridiag_solve(gpcsd_ctx *c, const double *W, double *B, const double *es,
     g.npad = tridiag_solve_npad(npmax);
     // Trials per pass: 64 (a lane each: one pass for up to 64 trials, 131 KB of LDS and 336 registers per lane: nothing else lives
     // on a CU beside such a workgroup) or 32 (two passes for 50 trials; 66 KB, 193 registers: two per CU, and other streams'
-    // workgroups beside them).  Same recurrences per trial, same bits.  The caller says which (gpcsd_ctx::solve_pass): the paired
+    // workgroups beside them).  Same recurrences per trial, same bits.  The caller says which (`hint`, PredCall::solve_pass): the paired
     // call of a step loop WITHOUT announcements asks for 32 -- the next step's eigen-chains start while this solve runs, and their
     // spatial Gram assembly took 204 us beside the wide form against 91 alone (0.901 against 0.941 ms per cfg3 step; with
     // announcements the chains are not there to be disturbed and the narrow form's second pass costs 2.4 %: 0.811 against 0.792).
     // Up to 32 trials the narrow form is one pass as well and always taken.  GPCSD_TS_P=32|64 forces one (A/B).
     static const int forced = getenv("GPCSD_TS_P") ? (atoi(getenv("GPCSD_TS_P")) == 32 ? 32 : 64) : 0;
-    const int P = pass ? pass : forced ? forced : (R <= 32 || c->solve_pass == 32) ? 32 : TS_P_DEFAULT;     // (pass: the caller's choice first)
+    const int P = pass ? pass : forced ? forced : (R <= 32 || hint == 32) ? 32 : TS_P_DEFAULT;     // (pass: the debug entry point's choice first)
     const size_t lds = tridiag_solve_lds(npmax, P);
     static size_t attr_dev[64][2] = {};            // (per device: the attribute belongs to the device's copy of the kernel)
     size_t *attr = attr_dev[c->device & 63];

@@ -158,11 +158,11 @@ bool k_ll_tridiag(gpcsd_ctx *c, const double *W, const double *es, const double 
 // The same systems solved: B[x'][r][p block] = (es[x'] amax_p T_p + sig2 I)^-1 W[x'][r][p block] (B may be W).  The posterior mean
 // in the basis U (x) Q -- what (W V) / D is in the basis U (x) V -- without the temporal eigenvectors.
 // k_tridiag_solve_pass: trials per pass of the kernel for column blocks of up to npmax (its z lives in LDS); 0 = unsupported.
-// pass: 0 = the launcher's choice (GPCSD_TS_P, the trial count, gpcsd_ctx::solve_pass), 32 or 64 = that form.
+// pass: 0 = the launcher's choice (GPCSD_TS_P, then the caller's hint -- PredCall::solve_pass --, then the trial count), 32 or 64 = that form.
 int k_tridiag_solve_pass(int npmax, int R);
 void k_tridiag_solve(gpcsd_ctx *c, const double *W, double *B, const double *es, const double *const d[2], const double *const e[2],
                      const double *const amax[2], const double *sig, int nx, int R, int nt, const int np[2], const int c0[2],
-                     hipStream_t s, int pass = 0);
+                     hipStream_t s, int pass = 0, int hint = 0);
 void k_add_diag(gpcsd_ctx *c, double *A, int n, double v, hipStream_t s, const HpDev *tab = nullptr, int B = 1, long s_out = 0);
 void k_shift_copy(gpcsd_ctx *c, const double *src, double *dst, int n, double v, hipStream_t s);     // dst = src + v
 void k_sum_partials(gpcsd_ctx *c, double *out, const double *P, long n, int parts, hipStream_t s);

@@ -140,13 +140,14 @@ def test_pipeline_over_panel_counts_and_odd_grids(nt):
     assert np.max(np.abs(vals[True][1] - ref["csd"])) <= 1e-8 * sc
 
 
-@pytest.mark.parametrize("form", ["fenced", "paired", "resident", "class_api"])
+@pytest.mark.parametrize("form", ["fenced", "paired", "resident", "class_api", "async_profiled"])
 def test_a_gate_that_gives_up_is_a_scheduling_miss_and_the_call_is_evaluated_again(form):
     """ADVICE r5 (wy.hip gate): when the tridiagonalisation is not running beside the launch that waits for it (kernels serialised by
     a profiler, an oversubscribed card) the gate's bounded wait runs out.  That is not a numerical failure: the stage launch leaves
     the unfinished reflectors alone, and the collecting call switches the pipeline off for the context (latched), counts the miss
     and evaluates again unpipelined -- the caller sees the unpipelined result, no LinAlgError.  Forced here with a patience of zero
-    ticks (gpcsd_q_pipeline_stats), through every call form that can carry a pipelined chain."""
+    ticks (gpcsd_q_pipeline_stats), through every call form that can carry a pipelined chain.  async_profiled: under fenced profiling
+    a queued log-likelihood is evaluated when it is queued and handed over at the wait -- which replays it like any other."""
     from gpcsd_amd import _hip
     R = 16
     w, m, lfp = _step_model(R)
@@ -181,6 +182,13 @@ def test_a_gate_that_gives_up_is_a_scheduling_miss_and_the_call_is_evaluated_aga
             ctx.q_pipeline(True)
             ctx.predict_resident(hp0, z, w["t"], _hip.PRED_CSD, want_lists=True)
             # (no synchronize: gpcsd_fetch itself collects the queued prediction's status -- and evaluates it again -- before it copies)
+        elif form == "async_profiled":
+            ctx.prof_enable(1)
+            ctx.loglik_parts_async(hp)
+            got_ll = ctx.loglik_parts_wait()                  # (raises LinAlgError where the wait hands a status 7 through)
+            assert ctx.q_pipeline_stats() == (False, miss0 + 1)
+            ctx.prof_enable(0)
+            ctx.predict_resident(hp0, z, w["t"], _hip.PRED_CSD, want_lists=True)      # (the pipeline stays latched off)
         else:
             got_ll = None
             ll_class = float(m.loglik())
@@ -199,6 +207,7 @@ def test_a_gate_that_gives_up_is_a_scheduling_miss_and_the_call_is_evaluated_aga
         ctx.q_pipeline_stats(gate_ticks=20000000)
         assert tuple(ctx.loglik_parts(hp)) == tuple(want_ll)
     finally:
+        ctx.prof_enable(0)
         ctx.q_pipeline_stats(gate_ticks=20000000)
         ctx.q_pipeline(True)
 
@@ -263,3 +272,42 @@ def test_interleaved_call_forms_replay_their_own_graphs():
     ll_ref = O.loglik(geom, ohp, lfp)
     print("interleaved forms: loglik vs oracle %.1e" % (abs(ll - ll_ref) / abs(ll_ref)))
     assert abs(ll - ll_ref) <= 1e-9 * abs(ll_ref)
+
+
+def test_a_refused_queued_call_copies_nothing_and_leaves_the_queue_as_it_was():
+    """A queued call keeps a copy of its hyper-parameters for the status-7 replay.  The copy is made only after the struct has been
+    validated: an n_sig2n that is neither 1 nor nx, over a one-element array, is refused by gpcsd_loglik_parts_async and
+    gpcsd_loglik_predict_async with the code the synchronous call gives, nothing is left pending, and the context computes on as
+    before.  The 24 x 131 x 16 model of the interleaved test."""
+    import ctypes
+    import bench
+    from gpcsd_amd import _hip
+    nt, R = 131, 16
+    w = bench.workload("cfg2")
+    w["nt"] = nt
+    w["t"] = 0.5 * np.arange(float(nt))[:, None]
+    m = bench.build_model(w, np.zeros((w["nx"], nt, 1)))
+    m.update_lfp(bench.synth_data(w, m, R, seed=nt), w["t"])
+    ctx = m._sync_device()
+    hp, k1 = m._hparams(m.JITTER)
+    hp0, k0 = m._hparams(0.0)
+    want = ctx.loglik_parts(hp)
+    bad = _hip.HParams()
+    ctypes.memmove(ctypes.byref(bad), ctypes.byref(hp), ctypes.sizeof(bad))
+    one = (ctypes.c_double * 1)(0.05)
+    bad.n_sig2n = 5                                           # neither 1 nor nx = 24
+    bad.sig2n = ctypes.cast(one, ctypes.POINTER(ctypes.c_double))
+    lib, h = ctx._lib, ctx._h
+    out = np.empty(2)
+    out_p = out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    code = lib.gpcsd_loglik_parts(h, ctypes.byref(bad), out_p)
+    assert code < 0
+    za = np.ascontiguousarray(w["x"], dtype=np.float64)
+    ta = np.ascontiguousarray(w["t"], dtype=np.float64).reshape(-1)
+    zp, tp = (a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) for a in (za, ta))
+    assert lib.gpcsd_loglik_parts_async(h, ctypes.byref(bad)) == code
+    for ll, pr in ((bad, hp0), (hp, bad)):
+        assert lib.gpcsd_loglik_predict_async(h, ctypes.byref(ll), ctypes.byref(pr), zp, za.shape[0], tp, ta.size, _hip.PRED_CSD, 1) == code
+    assert lib.gpcsd_loglik_parts_wait(h, out_p) < 0
+    assert "no asynchronous evaluation pending" in lib.gpcsd_last_error(h).decode()
+    assert tuple(ctx.loglik_parts(hp)) == tuple(want)
