@@ -148,6 +148,9 @@ SIGNATURES = {
     "gpcsd_predict_resident": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _I]),
     "gpcsd_predict_at": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _DP, _DP, _DP, _DP]),
     "gpcsd_predict_at_resident": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _I]),
+    "gpcsd_predict_var": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _DP, _DP, _DP, _DP]),
+    "gpcsd_predict_var_resident": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I]),
+    "gpcsd_var_contract": (_I, [_P, _DP, _I, _I, _DP, _I, _I, _DP, _DP, _DP]),
     "gpcsd_fetch": (_I, [_P, ctypes.c_char_p, _DP, _L]),
     "gpcsd_device_buffer": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
     "gpcsd_sample_prior": (_I, [_P, ctypes.POINTER(HParams), _I, _DP, _I, _DP]),
@@ -826,6 +829,40 @@ class Context:
         tstar = _arr(tstar).reshape(-1)
         fn = self._lib.gpcsd_predict_at_resident if at else self._lib.gpcsd_predict_resident
         self._check(fn(self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size, int(type_code), int(bool(want_lists))))
+
+    def predict_var(self, hp, z, tstar, type_code):
+        """Posterior variances (gpcsd_predict_var) as host arrays: dict with "csd" / "lfp" (nz, ntstar) and "csd_list" / "lfp_list"
+        (C, nz, ntstar) for the requested type."""
+        z = _arr(z)
+        tstar = _arr(tstar).reshape(-1)
+        nz, C = z.shape[0], hp.n_temporal
+        bufs = {}
+        for name, bit in (("csd", PRED_CSD), ("lfp", PRED_LFP)):
+            on = bool(type_code & bit)
+            bufs[name] = pinned_pool.empty((nz, tstar.size)) if on else None
+            bufs[name + "_list"] = pinned_pool.empty((C, nz, tstar.size)) if on else None
+        self._check(self._lib.gpcsd_predict_var(self._h, ctypes.byref(hp), _ptr(z), nz, _ptr(tstar), tstar.size, int(type_code),
+                                                _ptr(bufs["csd_list"]), _ptr(bufs["csd"]), _ptr(bufs["lfp_list"]), _ptr(bufs["lfp"])))
+        return {k: v for k, v in bufs.items() if v is not None}
+
+    def predict_var_resident(self, hp, z, tstar, type_code):
+        """The same into the device buffers "pred_var_csd", "pred_var_lfp" and their "_list" forms only; read back with fetch()."""
+        z = _arr(z)
+        tstar = _arr(tstar).reshape(-1)
+        self._check(self._lib.gpcsd_predict_var_resident(self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size,
+                                                         int(type_code)))
+
+    def var_contract(self, G, P, C, prior_s, kd):
+        """out (C + 1, nz, nts): prior_s[z] kd[c] - sum_k G[z, k] P[k, c * nts + j]**2, and the component sum's plane (the sum taken
+        before the square) last.  G (nz, K), P (K, C * nts)."""
+        G, P, prior_s, kd = _arr(G), _arr(P), _arr(prior_s).reshape(-1), _arr(kd).reshape(-1)
+        nz, K = G.shape
+        if P.shape[0] != K or P.shape[1] % C or prior_s.size != nz or kd.size != C:
+            raise ValueError("var_contract: G (nz, K), P (K, C * nts), prior_s (nz), kd (C)")
+        nts = P.shape[1] // C
+        out = np.empty((C + 1, nz, nts))
+        self._check(self._lib.gpcsd_var_contract(self._h, _ptr(G), nz, K, _ptr(P), int(C), nts, _ptr(prior_s), _ptr(kd), _ptr(out)))
+        return out
 
     def fetch(self, name, shape):
         out = pinned_pool.empty(shape)

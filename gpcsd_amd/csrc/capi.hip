@@ -133,11 +133,12 @@ void fwd_weights(gpcsd_ctx *c, const Geo &g, const double *pts, int n, double R,
     else k_fwd_weights_2d(c, pts, n, g.gx1, g.gw1, g.ngl1, g.gx2, g.gw2, g.ngl2, R, eps, A, s);
 }
 
-// Kphi(nx, nxp) = A Kgl Axp^T (+ jitter I when square and jitter != 0)     covariances.py:74-96 / :204-232
-// pfx names the scratch buffers: the spatial chain ("ks_", on its own stream) and the cross-covariance builds of predict
-// ("kx_", main stream) run concurrently and must not share them.
-void build_kphi(gpcsd_ctx *c, const Geo &g, double R, double eps, const double *ell, const double *xp, int nxp, double jitter,
-                double *out, hipStream_t s, const char *pfx = "kx_") {
+// The first two factors of Kphi = A Kgl Axp^T for the points of g: A (forward weights) and T = A Kgl, in the scratch buffers named
+// by pfx
+struct KphiAT {
+    double *A, *T;
+};
+KphiAT kphi_AT(gpcsd_ctx *c, const Geo &g, double R, double eps, const double *ell, hipStream_t s, const char *pfx) {
     const int G = g.G();
     const std::string P(pfx);
     double *A = c->buf<double>(P + "A", (size_t)g.nx * G);
@@ -179,6 +180,17 @@ void build_kphi(gpcsd_ctx *c, const Geo &g, double R, double eps, const double *
         v.prof_name = "gemm_Ks_K1U";
         gemm_f64(c, v, s);
     }
+    return {A, T};
+}
+// Kphi(nx, nxp) = A Kgl Axp^T (+ jitter I when square and jitter != 0)     covariances.py:74-96 / :204-232
+// pfx names the scratch buffers: the spatial chain ("ks_", on its own stream) and the cross-covariance builds of predict
+// ("kx_", main stream) run concurrently and must not share them.
+void build_kphi(gpcsd_ctx *c, const Geo &g, double R, double eps, const double *ell, const double *xp, int nxp, double jitter,
+                double *out, hipStream_t s, const char *pfx = "kx_") {
+    const int G = g.G();
+    const std::string P(pfx);
+    const KphiAT at = kphi_AT(c, g, R, eps, ell, s, pfx);
+    double *const A = at.A, *const T = at.T;
     const double *Axp = A;
     int n2 = g.nx;
     if (xp) {
@@ -211,6 +223,18 @@ void build_kphi(gpcsd_ctx *c, const Geo &g, double R, double eps, const double *
         gemm_f64(c, d2, s);
     }
     if (jitter != 0.0 && n2 == g.nx) k_add_diag(c, out, g.nx, jitter, s);
+}
+
+// diag(compKphi) at the nz sites z themselves: out[z] = (A_z Kgl A_z^T)[z][z], the prior variance of the potential there --
+// build_kphi's own factors for the sites in place of the electrodes (same launches, same operation order), then the row-wise dot
+// of T_z = A_z Kgl with A_z instead of the full product.  Scratch "kv_": beside the cross-covariance builds' "kx_".
+void build_kphi_diag(gpcsd_ctx *c, const Geo &g, double R, double eps, const double *ell, const double *z, int nz, double *out,
+                     hipStream_t s) {
+    Geo gz = g;
+    gz.x = z;
+    gz.nx = nz;
+    const KphiAT at = kphi_AT(c, gz, R, eps, ell, s, "kv_");
+    k_rowdot(c, at.T, at.A, nz, g.G(), out, s);
 }
 
 // Kphig(nx, nz) = A Kcross, Kcross[g, z] = SE(gl_g, z)                     covariances.py:58-72 / :188-202

@@ -722,29 +722,20 @@ static bool pred_unfold_chunked(gpcsd_ctx *c, const PredCall &q, PredUnfoldDesc 
 struct PredFullFront {
     double *Bm, *M1, *Kts;       // (nx, R, nt); (2, nz, nx): CSD, LFP; (C, ntstar, nt) = cov_c.compute_Kt(tstar)
 };
-static PredFullFront predict_full_front(gpcsd_ctx *c, const gpcsd_hparams *hp, EigState &e, const double *z, int nz, const double *tstar,
-                                        int ntstar, int type) {
+// The part of it that reads no trial data (all a posterior variance needs): sites and times to the device, the cross-covariances
+// with M1 = Kc^T Qs per requested output and the cross Grams -- everything that needs only Qs, queued before the join, i.e. it runs
+// beside the temporal eigensolver -- then the join.
+static void pred_cross_front(gpcsd_ctx *c, const gpcsd_hparams *hp, EigState &e, const double *z, int nz, const double *tstar, int ntstar,
+                             int type, PredFullFront &f) {
     const Geo g = resident_geo(c);
-    const int nx = c->nx, nt = c->nt, R = c->ntrials, C = hp->n_temporal;
-    const long RT = (long)R * nt;
+    const int nx = c->nx, nt = c->nt, C = hp->n_temporal;
     hipStream_t s = c->stream;
-    double *W = c->buf<double>("proj_W", (size_t)nx * RT);
-    PredFullFront f;
-    f.Bm = c->buf<double>("pred_B", (size_t)nx * RT);
-    GemmDesc g1;                          // W = Qs^T Y
-    g1.M = nx; g1.N = (int)RT; g1.K = nx;
-    g1.A = e.Qs; g1.lda = nx; g1.transA = true;
-    g1.B = c->d_lfp; g1.ldb = RT; g1.C = W; g1.ldc = RT;
-    g1.prof_name = "gemm_proj_spatial";
-    gemm_f64(c, g1, s);
     double *dz = c->upload_cached<double>("pred_z", z, (size_t)nz * g.dim);
     double *dts = c->upload_cached<double>("pred_tstar", tstar, ntstar);
     const double *t = (const double *)c->bufs["time_t"].p;
     double *Kc = c->buf<double>("pred_Kcross", (size_t)nx * nz);
     f.Kts = c->buf<double>("pred_Ktstar", (size_t)C * ntstar * nt);
     f.M1 = c->buf<double>("pred_M1", (size_t)2 * nz * nx);
-    // Everything that needs only Qs is queued before the join, i.e. it runs beside the temporal eigensolver:
-    // cross-covariances Kc, M1 = Kc^T Qs for the requested outputs, and the prediction-time temporal Grams.
     for (int which = 1; which <= 2; ++which) {
         if (!(type & which)) continue;
         if (which == 1) build_kphig(c, g, hp->R, hp->eps, hp->ell_s, dz, nz, Kc, s);        // gpcsd1d.py:273
@@ -760,6 +751,22 @@ static PredFullFront predict_full_front(gpcsd_ctx *c, const gpcsd_hparams *hp, E
     for (int cc = 0; cc < C; ++cc)
         temporal_cross_gram(c, hp, cc, dts, ntstar, t, nt, f.Kts + (size_t)cc * ntstar * nt, s);
     join_temporal(c, e, nullptr, false);      // predict never reads sum(log D)
+}
+static PredFullFront predict_full_front(gpcsd_ctx *c, const gpcsd_hparams *hp, EigState &e, const double *z, int nz, const double *tstar,
+                                        int ntstar, int type) {
+    const int nx = c->nx, nt = c->nt, R = c->ntrials;
+    const long RT = (long)R * nt;
+    hipStream_t s = c->stream;
+    double *W = c->buf<double>("proj_W", (size_t)nx * RT);
+    PredFullFront f;
+    f.Bm = c->buf<double>("pred_B", (size_t)nx * RT);
+    GemmDesc g1;                          // W = Qs^T Y
+    g1.M = nx; g1.N = (int)RT; g1.K = nx;
+    g1.A = e.Qs; g1.lda = nx; g1.transA = true;
+    g1.B = c->d_lfp; g1.ldb = RT; g1.C = W; g1.ldc = RT;
+    g1.prof_name = "gemm_proj_spatial";
+    gemm_f64(c, g1, s);
+    pred_cross_front(c, hp, e, z, nz, tstar, ntstar, type, f);
     GemmDesc g2;                          // Bm = (W Qt) / D
     g2.M = nx * R; g2.N = nt; g2.K = nt;
     g2.A = W; g2.lda = nt; g2.B = e.Qt; g2.ldb = nt; g2.C = f.Bm; g2.ldc = nt;
@@ -1261,6 +1268,94 @@ extern "C" int gpcsd_predict_at(gpcsd_ctx *c, const gpcsd_hparams *hp, const dou
     PredSink out;
     out.sum[0] = csd; out.list[0] = csd_list; out.sum[1] = lfp; out.list[1] = lfp_list;
     pred_download(c, q, out);
+    c->sync();
+    return rc;
+    GP_API_END(c)
+}
+
+// Posterior VARIANCE at the sites and times of gpcsd_predict_at (gpcsd_predict_var; no reference counterpart), of the model whose
+// mean that call returns: D = es (x) et + sig2n exactly as front_half(c, hp, 0.0) builds it.  With M1 = Kcross^T Qs and
+// P_c[i'][j] = sum_i Qt[i][i'] k_c(t*_j, t_i) the explained part of component c at (z, t*_j) is
+//   sum_{x',i'} M1[z][x']^2 P_c[i'][j]^2 / D[x'][i']  =  sum_i' G[z][i'] P_c[i'][j]^2,     G[z][i'] = sum_x' M1[z][x']^2 / D[x'][i'],
+// G formed first and once (it depends on neither t* nor the component), every sum over non-negative terms; the component SUM has
+// (sum_c P_c)^2 in place of P_c^2 -- the components are correlated a posteriori, so it is a plane of its own.  Reads no trial data.
+// Outputs: pred_var_csd / pred_var_lfp (nz, ntstar), pred_var_csd_list / pred_var_lfp_list (C, nz, ntstar).
+static int predict_var_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar, int type) {
+    GP_REQUIRE(z && tstar && nz > 0 && ntstar > 0, -3, "predict_var: bad arguments");
+    GP_REQUIRE(type >= 1 && type <= 3, -3, "predict_var: type must be CSD(1), LFP(2) or BOTH(3)");
+    GP_REQUIRE(hp != nullptr, -3, "null hparams");
+    GP_REQUIRE(c->d_lfp != nullptr, -4, "lfp not set (call gpcsd_set_lfp)");
+    GP_REQUIRE(!uses_host_kt(hp), -3, "predict_var: a user-defined temporal covariance (GPCSD_KIND_HOST) has no prior variance "
+               "k_c(t*, t*) on the device; only the built-in kinds are supported");
+    // (checked before tstar is read: one row of the concatenated P_c is a flat GEMM operand row)
+    GP_REQUIRE((long)std::max(hp->n_temporal, 1) * ntstar < GPCSD_MAX_GEMM_LD_KMAJOR, GPCSD_ERR_CAPACITY,
+               "predict_var: n_temporal * ntstar = %ld exceeds the capacity of one operand row (%ld doubles; GPCSD_MAX_GEMM_LD_KMAJOR)",
+               (long)std::max(hp->n_temporal, 1) * ntstar, (long)GPCSD_MAX_GEMM_LD_KMAJOR);
+    // the scratch of the prediction calls is rewritten below: whatever an earlier queued prediction still owes is collected first
+    if (int rc = drain_async(c)) return rc;
+    EigState e = front_half(c, hp, 0.0);           // no jitter, as predict (gpcsd1d.py:258)
+    const Geo g = resident_geo(c);
+    const int nx = c->nx, nt = c->nt, C = hp->n_temporal;
+    hipStream_t s = c->stream;
+    PredFullFront f{nullptr, nullptr, nullptr};
+    pred_cross_front(c, hp, e, z, nz, tstar, ntstar, type, f);
+    double *Pc = c->buf<double>("pred_Pc", (size_t)C * nt * ntstar);
+    double *G = c->buf<double>("pred_var_G", (size_t)nz * nt);
+    double *prior = c->buf<double>("pred_var_prior", (size_t)nz);
+    const double *dz = (const double *)c->bufs["pred_z"].p;
+    for (int cc = 0; cc < C; ++cc) {
+        GemmDesc gp;                      // Pcat[i'][cc*ntstar + j] = sum_i Qt[i][i'] Ktstar_cc[j][i]: the TRAINING axis contracted
+        gp.M = nt; gp.N = ntstar; gp.K = nt;
+        gp.A = e.Qt; gp.lda = nt; gp.transA = true; gp.B = f.Kts + (size_t)cc * ntstar * nt; gp.ldb = nt; gp.transB = true;
+        gp.C = Pc + (size_t)cc * ntstar; gp.ldc = (long)C * ntstar;
+        gp.prof_name = "gemm_pred_Pc";
+        gemm_f64(c, gp, s);
+    }
+    const size_t out_elems = (size_t)nz * ntstar;
+    for (int which = 1; which <= 2; ++which) {
+        if (!(type & which)) continue;
+        // prior variance of the spatial factor at the sites: compute_Ks has a unit diagonal (covariances.py:50-56, 177-186); the
+        // potential's is the diagonal of compKphi at the sites themselves (covariances.py:74-96, 204-232)
+        if (which == 1) k_fill(c, prior, nz, 1.0, s);
+        else build_kphi_diag(c, g, hp->R, hp->eps, hp->ell_s, dz, nz, prior, s);
+        VarDesc v1;                       // G[z][i'] = sum_x' M1[z][x']^2 Dinv[x'][i']
+        v1.A = f.M1 + (size_t)(which - 1) * nz * nx; v1.lda = nx; v1.B = e.Dinv; v1.ldb = nt;
+        v1.nrow = nz; v1.ncol = nt; v1.K = nx; v1.sq_a = true; v1.list = G;
+        v1.prof_name = "gemm_var_G";
+        gemm_var(c, v1, s);
+        VarDesc v2;                       // var_c[z][j] = prior[z] k_c(0) - sum_i' G[z][i'] P_c[i'][j]^2, and the component sum's plane
+        v2.A = G; v2.lda = nt; v2.B = Pc; v2.ldb = (long)C * ntstar;
+        v2.nrow = nz; v2.ncol = ntstar; v2.K = nt; v2.C = C;
+        v2.prior = prior;
+        // k_c(t*, t*) = sigma2_c for both built-in kinds (covariances.py:270, 304), rounded as the Gram builders round it
+        for (int cc = 0; cc < C; ++cc) v2.kd[cc] = c->gram_fp32 ? (double)(float)hp->sigma2_t[cc] : hp->sigma2_t[cc];
+        v2.list = c->buf<double>(which == 1 ? "pred_var_csd_list" : "pred_var_lfp_list", out_elems * C);
+        v2.sum = c->buf<double>(which == 1 ? "pred_var_csd" : "pred_var_lfp", out_elems);
+        gemm_var(c, v2, s);
+    }
+    return finish_call(c, e, nullptr, 0);
+}
+
+extern "C" int gpcsd_predict_var_resident(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar,
+                                          int ntstar, int type) {
+    GP_API_BEGIN(c)
+    return predict_var_impl(c, hp, z, nz, tstar, ntstar, type);
+    GP_API_END(c)
+}
+
+extern "C" int gpcsd_predict_var(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar,
+                                 int type, double *csd_var_list, double *csd_var, double *lfp_var_list, double *lfp_var) {
+    GP_API_BEGIN(c)
+    const int rc = predict_var_impl(c, hp, z, nz, tstar, ntstar, type);
+    if (rc < 0) return rc;
+    const size_t out_elems = (size_t)nz * ntstar;
+    double *const sum[2] = {csd_var, lfp_var}, *const list[2] = {csd_var_list, lfp_var_list};
+    for (int w = 0; w < 2; ++w) {
+        if (!(type & (w + 1))) continue;
+        if (sum[w]) c->download(sum[w], c->bufs[w ? "pred_var_lfp" : "pred_var_csd"].p, out_elems * sizeof(double));
+        if (list[w])
+            c->download(list[w], c->bufs[w ? "pred_var_lfp_list" : "pred_var_csd_list"].p, out_elems * hp->n_temporal * sizeof(double));
+    }
     c->sync();
     return rc;
     GP_API_END(c)

@@ -446,6 +446,35 @@ extern "C" int gpcsd_gemm(gpcsd_ctx *c, int transA, int transB, int M, int N, in
     GP_API_END(c)
 }
 
+// The second product of a posterior variance alone, on host arrays (no reference counterpart; gemm_f64.hip: gemm_var_kernel):
+// out (C + 1, nz, nts), planes c < C = prior_s[z] kd[c] - sum_k G[z][k] P[k][c * nts + j]^2, plane C = prior_s[z] sum_c kd[c] -
+// sum_k G[z][k] (sum_c P[k][c * nts + j])^2.  G (nz, K), P (K, C * nts), prior_s (nz), kd (C).
+extern "C" int gpcsd_var_contract(gpcsd_ctx *c, const double *G, int nz, int K, const double *P, int C, int nts, const double *prior_s,
+                                  const double *kd, double *out) {
+    GP_API_BEGIN(c)
+    GP_REQUIRE(G && P && prior_s && kd && out && nz > 0 && K > 0 && nts > 0, -3, "var_contract: bad arguments");
+    GP_REQUIRE(C >= 1 && C <= GPCSD_MAX_TEMPORAL, -3, "var_contract: C=%d outside [1,%d]", C, GPCSD_MAX_TEMPORAL);
+    GP_REQUIRE((long)C * nts < GPCSD_MAX_GEMM_LD_KMAJOR && K < (1 << 22), GPCSD_ERR_CAPACITY,
+               "var_contract: C * nts = %ld (or K = %d) exceeds the capacity of one operand row", (long)C * nts, K);
+    const size_t plane = (size_t)nz * nts;
+    double *dG = c->upload<double>("op_in0", G, (size_t)nz * K);
+    double *dP = c->upload<double>("op_in1", P, (size_t)K * C * nts);
+    double *dpr = c->upload<double>("op_in2", prior_s, (size_t)nz);
+    double *dO = c->buf<double>("op_out", plane * (C + 1));
+    VarDesc v;
+    v.A = dG; v.lda = K; v.B = dP; v.ldb = (long)C * nts;
+    v.nrow = nz; v.ncol = nts; v.K = K; v.C = C;
+    v.prior = dpr;
+    for (int i = 0; i < C; ++i) v.kd[i] = kd[i];
+    v.list = dO; v.sum = dO + plane * C;
+    gemm_var(c, v, c->stream);
+    c->download(out, dO, plane * (C + 1) * sizeof(double));
+    c->sync();
+    if (c->prof_mode == 1) c->prof_collect();
+    return 0;
+    GP_API_END(c)
+}
+
 __global__ void fill_pattern_kernel(double *p, long n, double a) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         unsigned long long h = (unsigned long long)i * 6364136223846793005ull + 1442695040888963407ull;

@@ -1014,6 +1014,225 @@ void gemm_pred_at(gpcsd_ctx *c, const PredAtDesc &d, hipStream_t s) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The two products of a posterior variance (gpcsd_predict_var), VarDesc in kernels.hpp:
+//
+//   SQA:   G[z][i']       = sum_x' M1[z][x']^2 Dinv[x'][i']
+//   else:  out[c][z][j]   = prior[z] kd[c]       - sum_i' G[z][i'] P_c[i'][j]^2                 plane c < C
+//          out[C][z][j]   = prior[z] sum_c kd[c] - sum_i' G[z][i'] (sum_c P_c[i'][j])^2         plane C
+//
+// One operand is squared in registers between its global load and its LDS store, so neither M1 o M1 nor P o P is ever written
+// to memory; the plane of the component sum adds the C columns of a slot in registers (index order) before it squares.  Every
+// term of every sum is non-negative: the only cancellation of a variance is the subtraction in the epilogue, one fused
+// multiply-add per element.  A workgroup owns a 64 x 64 tile (rows z, columns i' / j: the lanes of a wave run along the output's
+// innermost index), four waves of 2 x 2 fragments; grid y = plane.  Edges as gemm_pred_at_kernel: a row or column past the end
+// reads the last valid one (its accumulators are never stored), the last K tile is zero-masked in LDS.
+struct VarK {
+    const double *A;             // [nrow][K] row-major
+    long lda;
+    const double *B;             // [K][C * ncol] row-major
+    long ldb;
+    int nrow, ncol, K, C;
+    const double *prior;         // [nrow], or nullptr: the product itself is stored
+    double kd[GPCSD_MAX_TEMPORAL];
+    double kd_sum;
+    double *list;                // [plane < C][nrow][ncol]
+    double *sum;                 // plane C
+    int tiles_n;
+};
+
+template <bool SQA>
+__global__ __launch_bounds__(256) void gemm_var_kernel(VarK g) {
+    constexpr int NT = 256, BK = 16, BM = 64, BN = 64;
+    using TileA = Tile<BM, false, NT, BK>;    // G / M1: global [rows][K]
+    using TileB = Tile<BN, true, NT, BK>;     // Pcat / Dinv: global [K][cols]
+    __shared__ double lds[2 * (TileA::LDS_ELEMS + TileB::LDS_ELEMS)];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wr = wid >> 1, wc = wid & 1;
+    const int tile_n = blockIdx.x % g.tiles_n, tile_m = blockIdx.x / g.tiles_n;
+    const int m0 = tile_m * BM, n0 = tile_n * BN;
+    const int plane = blockIdx.y;                              // wave-uniform
+    const bool all = plane == g.C;                             // the plane of the component sum
+    const int ncomp = all ? g.C : 1;
+    const int fr = lane & 15, fq = lane >> 4;
+
+    d4 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
+
+    int oa0, ka0, ob0, kb0;
+    TileA::slot0(tid, oa0, ka0);
+    TileB::slot0(tid, ob0, kb0);
+    double *const swA = lds + TileA::lds_index(oa0, ka0);
+    double *const swB = lds + 2 * TileA::LDS_ELEMS + TileB::lds_index(ob0, kb0);
+    const double *const srA = lds + TileA::lds_index(wr * 32 + fr, fq);
+    const double *const srB = lds + 2 * TileA::LDS_ELEMS + TileB::lds_index(wc * 32 + fr, fq);
+    using Buf0 = std::integral_constant<int, 0>;
+    using Buf1 = std::integral_constant<int, 1>;
+
+    const int K = g.K;
+    unsigned offA[TileA::PER_THREAD], offB[TileB::PER_THREAD];
+    TileA::setup(offA, g.lda, m0, g.nrow, tid);
+    TileB::setup(offB, g.ldb, n0, g.ncol, tid);
+    const double *const baseA = TileA::tile_base(g.A, g.lda, m0);
+    const double *const baseB = TileB::tile_base(g.B + (all ? 0L : (long)plane * g.ncol), g.ldb, n0);       // wave-uniform
+    const int cstep = g.ncol * 8;                              // bytes from one component's column to the next one's
+    const int nk = (K + BK - 1) / BK, nfull = K / BK;
+    double ra[TileA::PER_THREAD], rb[TileB::PER_THREAD];
+
+    auto load_full = [&](int t) {
+        TileA::gload(ra, TileA::rsrc(baseA, g.lda, t), 0, offA);
+        const __amdgpu_buffer_rsrc_t rsb = TileB::rsrc(baseB, g.ldb, t);
+        TileB::gload(rb, rsb, 0, offB);
+        for (int cc = 1; cc < ncomp; ++cc) {                   // (wave-uniform: the sum plane only)
+            double rc[TileB::PER_THREAD];
+            TileB::gload(rc, rsb, cc * cstep, offB);
+#pragma unroll
+            for (int i = 0; i < TileB::PER_THREAD; ++i) rb[i] += rc[i];
+        }
+    };
+    auto load_any = [&](int t) {
+        if (t < nfull) {
+            load_full(t);
+        } else {                                               // partial K tile: out-of-range k reads the last valid one
+            const int kleft = K - t * BK;
+            TileA::gload_tail(ra, TileA::rsrc(baseA, g.lda, t), 0, g.lda, m0, g.nrow, kleft, tid);
+            const __amdgpu_buffer_rsrc_t rsb = TileB::rsrc(baseB, g.ldb, t);
+            TileB::gload_tail(rb, rsb, 0, g.ldb, n0, g.ncol, kleft, tid);
+            for (int cc = 1; cc < ncomp; ++cc) {
+                double rc[TileB::PER_THREAD];
+                TileB::gload_tail(rc, rsb, cc * cstep, g.ldb, n0, g.ncol, kleft, tid);
+#pragma unroll
+                for (int i = 0; i < TileB::PER_THREAD; ++i) rb[i] += rc[i];
+            }
+        }
+    };
+    auto store_any = [&](auto bufc, int t) {
+        constexpr int buf = decltype(bufc)::value;
+        if (SQA) {
+#pragma unroll
+            for (int i = 0; i < TileA::PER_THREAD; ++i) ra[i] *= ra[i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < TileB::PER_THREAD; ++i) rb[i] *= rb[i];
+        }
+        if (t < nfull) {
+            TileA::template sstore<false>(ra, swA + buf * TileA::LDS_ELEMS, 0, 0);
+            TileB::template sstore<false>(rb, swB + buf * TileB::LDS_ELEMS, 0, 0);
+        } else {
+            TileA::template sstore<true>(ra, swA + buf * TileA::LDS_ELEMS, ka0, K - t * BK);
+            TileB::template sstore<true>(rb, swB + buf * TileB::LDS_ELEMS, kb0, K - t * BK);
+        }
+    };
+    const int last_steps = (nk > nfull) ? (K - nfull * BK + 3) / 4 : BK / 4;
+    auto mma = [&](auto bufc, int steps) {
+        constexpr int buf = decltype(bufc)::value;
+        const double *sa = srA + buf * TileA::LDS_ELEMS;
+        const double *sb = srB + buf * TileB::LDS_ELEMS;
+#pragma unroll
+        for (int kk = 0; kk < BK / 4; ++kk) {
+            if (kk < steps) {                                  // wave-uniform
+                double a[2], b[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) a[i] = LDS_FRAG(sa + TileA::lds_index(i * 16, kk * 4));
+#pragma unroll
+                for (int j = 0; j < 2; ++j) b[j] = LDS_FRAG(sb + TileB::lds_index(j * 16, kk * 4));
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
+            }
+        }
+    };
+    load_any(0);
+    store_any(Buf0{}, 0);
+    __syncthreads();
+    int kt = 0;
+    for (; kt + 2 < nfull; kt += 2) {
+        load_full(kt + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        mma(Buf0{}, BK / 4);
+        __builtin_amdgcn_sched_barrier(0);
+        store_any(Buf1{}, kt + 1);
+        __syncthreads();
+        load_full(kt + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        mma(Buf1{}, BK / 4);
+        __builtin_amdgcn_sched_barrier(0);
+        store_any(Buf0{}, kt + 2);
+        __syncthreads();
+    }
+    if (kt + 1 < nk) {
+        load_any(kt + 1);
+        mma(Buf0{}, BK / 4);
+        store_any(Buf1{}, kt + 1);
+        __syncthreads();
+        if (kt + 2 < nk) {
+            load_any(kt + 2);
+            mma(Buf1{}, BK / 4);
+            store_any(Buf0{}, kt + 2);
+            __syncthreads();
+            mma(Buf0{}, last_steps);
+        } else {
+            mma(Buf1{}, last_steps);
+        }
+    } else {
+        mma(Buf0{}, last_steps);
+    }
+
+    // ---- epilogue: prior[z] kd - acc, one rounding; 16 consecutive columns per store instruction ----
+    double *const out = all ? g.sum : g.list + (long)plane * g.nrow * g.ncol;
+    double kdp = g.kd_sum;
+#pragma unroll
+    for (int cc = 0; cc < GPCSD_MAX_TEMPORAL; ++cc)
+        if (cc == plane && !all) kdp = g.kd[cc];               // (no dynamic index into the by-value argument)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+            const int row = m0 + wr * 32 + i * 16 + fq + 4 * r4;
+            if (row >= g.nrow) continue;
+            const double pk = g.prior ? g.prior[row] : 0.0;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int col = n0 + wc * 32 + j * 16 + fr;
+                if (col >= g.ncol) continue;
+                const double v = acc[i][j][r4];
+                out[(long)row * g.ncol + col] = g.prior ? __builtin_fma(pk, kdp, -v) : v;
+            }
+        }
+}
+
+void gemm_var(gpcsd_ctx *c, const VarDesc &d, hipStream_t s) {
+    GP_REQUIRE(d.nrow > 0 && d.ncol > 0 && d.K > 0 && d.C >= 1 && d.C <= GPCSD_MAX_TEMPORAL && d.A && d.B && d.list, -3,
+               "gemm_var: bad problem");
+    GP_REQUIRE(!d.sq_a || (d.C == 1 && !d.sum && !d.prior), -3, "gemm_var: the squared-A form is one plain product");
+    // 32-bit byte offsets inside one K tile of one block tile: 64 rows of A, 16 rows of B and the C components of a slot
+    GP_REQUIRE(d.lda < (1L << 22) && d.ldb < GPCSD_MAX_GEMM_LD_KMAJOR && (long)d.C * d.ncol <= d.ldb, GPCSD_ERR_CAPACITY,
+               "gemm_var: leading dimension %ld exceeds the capacity of one operand row", d.lda < (1L << 22) ? d.ldb : d.lda);
+    const long tiles = (long)ceil_div(d.nrow, 64) * ceil_div(d.ncol, 64);
+    GP_REQUIRE(tiles < (1L << 31), GPCSD_ERR_CAPACITY, "gemm_var: too many tiles");
+    const int planes = d.C + (d.sum ? 1 : 0);
+    ProfScope ps(c, d.prof_name, 2.0 * (double)d.nrow * d.ncol * (double)d.K * planes, s);
+    VarK k;
+    k.A = d.A; k.lda = d.lda; k.B = d.B; k.ldb = d.ldb;
+    k.nrow = d.nrow; k.ncol = d.ncol; k.K = d.K; k.C = d.C;
+    k.prior = d.prior;
+    k.kd_sum = 0.0;
+    for (int i = 0; i < GPCSD_MAX_TEMPORAL; ++i) {
+        k.kd[i] = i < d.C ? d.kd[i] : 0.0;
+        if (i < d.C) k.kd_sum += d.kd[i];                      // index order, as the component sum itself
+    }
+    k.list = d.list; k.sum = d.sum;
+    k.tiles_n = ceil_div(d.ncol, 64);
+    const dim3 grid((unsigned)tiles, (unsigned)planes);
+    if (d.sq_a) hipLaunchKernelGGL((gemm_var_kernel<true>), grid, dim3(256), 0, s, k);
+    else hipLaunchKernelGGL((gemm_var_kernel<false>), grid, dim3(256), 0, s, k);
+    GP_HIP(hipGetLastError());
+}
+
 // Deterministic final reduction of per-block partials (single workgroup, fixed tree).
 // A second workgroup may carry an unrelated reduction of the same shape (p2, n2 -> out2: the sum of log D partials of the
 // likelihood, which would otherwise be a launch of its own in the dependent tail of the call).

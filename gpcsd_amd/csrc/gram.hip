@@ -1263,6 +1263,28 @@ void k_sum_partials(gpcsd_ctx *c, double *out, const double *P, long n, int part
     GP_HIP(hipGetLastError());
 }
 
+// out[z] = sum_g T[z][g] A[z][g]: one workgroup per row, every thread its strided share in index order, then a fixed tree
+__global__ __launch_bounds__(256) void rowdot_kernel(const double *__restrict__ T, const double *__restrict__ A, int G,
+                                                     double *__restrict__ out) {
+    __shared__ double part[256];
+    const long row = blockIdx.x;
+    const double *t = T + row * G, *a = A + row * G;
+    double acc = 0.0;
+    for (int g = threadIdx.x; g < G; g += 256) acc = acc + t[g] * a[g];
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) part[threadIdx.x] = part[threadIdx.x] + part[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[row] = part[0];
+}
+void k_rowdot(gpcsd_ctx *c, const double *T, const double *A, int n, int G, double *out, hipStream_t s) {
+    GP_REQUIRE(n > 0 && G > 0, -3, "rowdot: empty problem");
+    hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)n), dim3(256), 0, s, T, A, G, out);
+    GP_HIP(hipGetLastError());
+}
+
 __global__ void fill_kernel(double *p, long n, double v) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = v;
 }

@@ -101,6 +101,27 @@ struct PredAtDesc {
 };
 void gemm_pred_at(gpcsd_ctx *c, const PredAtDesc &d, hipStream_t s);
 
+// The two products of a posterior variance (gpcsd_predict_var; gemm_f64.hip: gemm_var_kernel), one operand squared on its way to
+// LDS so that no squared copy exists in memory:
+//   sq_a:  out[z][i] = sum_k A[z][k]^2 B[k][i]                                  (G = (M1 o M1) Dinv; C = 1, prior = nullptr)
+//   else:  list[c][z][j] = prior[z] kd[c] - sum_k A[z][k] B[k][c * ncol + j]^2                                   c = 0..C-1
+//          sum[z][j]     = prior[z] sum_c kd[c] - sum_k A[z][k] (sum_c B[k][c * ncol + j])^2     (the components are correlated)
+// prior == nullptr: the plain product is stored (no subtraction).  One launch: grid y = the C (+ 1 when sum != nullptr) planes.
+struct VarDesc {
+    const double *A = nullptr;      // [nrow][K] row-major
+    long lda = 0;
+    const double *B = nullptr;      // [K][C * ncol] row-major
+    long ldb = 0;
+    int nrow = 0, ncol = 0, K = 0, C = 1;
+    bool sq_a = false;
+    const double *prior = nullptr;  // [nrow]
+    double kd[GPCSD_MAX_TEMPORAL] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double *list = nullptr;         // (C, nrow, ncol)
+    double *sum = nullptr;          // (nrow, ncol) or nullptr
+    const char *prof_name = "gemm_var";
+};
+void gemm_var(gpcsd_ctx *c, const VarDesc &d, hipStream_t s);
+
 // ---------------------------------------------------------------- batched hyper-parameter sets
 // Device image of gpcsd_hparams for batched evaluations (gpcsd_loglik_grad_batch): one entry per hyper-parameter set.  The
 // Gram builders / derivative kernels take an optional table: with `tab` they run once for all B sets (the set index is a grid
@@ -166,6 +187,9 @@ void k_tridiag_solve(gpcsd_ctx *c, const double *W, double *B, const double *es,
 void k_add_diag(gpcsd_ctx *c, double *A, int n, double v, hipStream_t s, const HpDev *tab = nullptr, int B = 1, long s_out = 0);
 void k_shift_copy(gpcsd_ctx *c, const double *src, double *dst, int n, double v, hipStream_t s);     // dst = src + v
 void k_sum_partials(gpcsd_ctx *c, double *out, const double *P, long n, int parts, hipStream_t s);
+// out[z] = sum_g T[z][g] A[z][g] (rows of G doubles): the diagonal of T A^T, i.e. of compKphi at the points themselves when
+// T = A Kgl (covariances.py:90,95 / :223,231) -- the prior variance of the potential at a prediction site
+void k_rowdot(gpcsd_ctx *c, const double *T, const double *A, int n, int G, double *out, hipStream_t s);
 // D[x*nt + i] = es[x]*et[i] + sig[x or 0]; also sumlog -> *sumlog_out (deterministic)
 // with a table (B sets): scalar noise from tab[b].sig2n when nsig == 1, else set b's list at sig + b * nx
 // Dinv (optional) = 1/D elementwise.  sumlog_out == nullptr: no final sum; the per-block partials stay in the ctx buffer

@@ -774,6 +774,51 @@ class GPCSDModel:
                 res = {k: sh.gather_trials(v) for k, v in res.items()}
         self._store_predictions(res, z, tstar)
 
+    _VAR_BUFFERS = (("csd", _hip.PRED_CSD, "pred_var_csd"), ("lfp", _hip.PRED_LFP, "pred_var_lfp"))
+
+    def predict_var(self, z, tstar, type="csd", resident=False):
+        """Posterior VARIANCE of CSD and/or LFP at sites z and arbitrary times tstar: the diagonal of the posterior covariance of the
+        model whose mean `predict_at(z, tstar)` returns (no jitter; a per-electrode noise list on the eigen-index as in loglik).  It
+        does not depend on the trials, so it is one (nz, ntstar) array per quantity.  Sets `csd_var` / `lfp_var` (the sum of the
+        temporal components -- NOT the sum of the entries of the list: the components are correlated a posteriori) and
+        `csd_var_list` / `lfp_var_list` (one array per temporal component), `t_var = tstar`, `x_var = z`; `csd_pred`, `lfp_pred`,
+        `t_pred` and `x_pred` are left as they are.  resident=True: zero-copy device views as in `predict`.
+
+        The LFP variance is that of the noise-free potential (no sig2n added).  Values are returned UNCLAMPED: where the data pin
+        the estimate down (var << prior) the final subtraction prior - explained may leave a slightly negative entry; that is the
+        caller's signal that the band is below the resolution of float64 there, not something to hide.  Under trial sharding every
+        rank computes the same arrays locally (no communication; `gather_predictions` does not apply).  User-defined temporal
+        covariances are not supported (no prior variance on the device): NotImplementedError.  No reference counterpart."""
+        if type not in ("csd", "lfp", "both"):
+            raise ValueError("type must be 'csd', 'lfp' or 'both'")
+        z = np.asarray(z, dtype=np.float64)
+        z2 = z.reshape(-1, 1) if self.dim == 1 else z
+        tstar = np.asarray(tstar)
+        if tstar.size < 1:
+            raise ValueError("tstar must hold at least one time")
+        if self._uses_host_kt():
+            raise NotImplementedError("predict_var: a user-defined temporal covariance has no prior variance k(t*, t*) on the device; "
+                                      "only GPCSDTemporalCovSE / GPCSDTemporalCovMatern components are supported")
+        ctx = self._sync_device()
+        hp, _keep = self._hparams(0.0)                     # no jitter, as predict
+        code = {"csd": _hip.PRED_CSD, "lfp": _hip.PRED_LFP, "both": _hip.PRED_BOTH}[type]
+        nz, nts, C = z2.shape[0], tstar.size, len(self.temporal_cov_list)
+        if resident:
+            ctx.predict_var_resident(hp, z2, tstar, code)
+            res = {}
+            for name, bit, buf in self._VAR_BUFFERS:
+                if code & bit:
+                    res[name] = ctx.device_array(buf, (nz, nts))
+                    res[name + "_list"] = ctx.device_array(buf + "_list", (C, nz, nts))
+        else:
+            res = ctx.predict_var(hp, z2, tstar, code)
+        for name in ("csd", "lfp"):
+            if res.get(name) is not None:
+                setattr(self, name + "_var_list", [res[name + "_list"][i] for i in range(C)])
+                setattr(self, name + "_var", res[name])
+        self.t_var = tstar
+        self.x_var = z
+
     def loglik_predict_many(self, param_sets, z, t, type="csd", resident=False, share_spatial=False):
         """loglik() and predict(z, t, type) under each of a LIST of hyper-parameter sets -- dicts as extract_model_params() returns
         them: the optima of every restart of a fit, a grid, posterior draws -- in order.  Returns the log-likelihoods, one per set;

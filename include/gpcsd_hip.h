@@ -295,6 +295,34 @@ int gpcsd_predict_at(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double *z, i
  * gpcsd_device_buffer.  This call waits for its own work: a numerical failure (rc > 0) is returned by the call itself. */
 int gpcsd_predict_at_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double *z, int nz,
                               const double *tstar, int ntstar, int type, int want_lists);
+/* Posterior VARIANCE of the CSD / LFP at sites z and ARBITRARY times tstar -- the diagonal of the posterior covariance of the model
+ * whose mean gpcsd_predict_at returns (no jitter; a per-electrode noise list on the eigen-index as utility_functions.py:54-63).  NO
+ * REFERENCE COUNTERPART: the reference has no predictive variance.  Per component c and for the component sum,
+ *   var_c[z, j]   = prior_s[z] sigma2_c       - k_c^T (Ks (x) Kt + sig2n I)^-1 k_c,      k_c = Kcross[:, z] (x) k_c(t*_j, t),
+ *   var_sum[z, j] = prior_s[z] sum_c sigma2_c - (sum_c k_c)^T (..)^-1 (sum_c k_c)         (NOT sum_c var_c: the components are
+ *                                                                                         correlated a posteriori),
+ * with prior_s = 1 for the CSD (the diagonal of compute_Ks, covariances.py:50-56, 177-186) and the diagonal of compKphi at the sites
+ * (covariances.py:74-96, 204-232) for the LFP, whose variance is that of the noise-free potential (no sig2n added).  Values are
+ * returned UNCLAMPED: where var << prior the subtraction may leave a slightly negative entry.  Reads no trial data (gpcsd_set_lfp
+ * must have fixed nx and nt); the cost does not depend on ntrials.  Arguments and `type` as gpcsd_predict_at; outputs (any may be
+ * NULL): *_var_list (n_temporal, nz, ntstar), *_var (nz, ntstar).  Capacity (n_temporal * ntstar >= GPCSD_MAX_GEMM_LD_KMAJOR) returns
+ * GPCSD_ERR_CAPACITY before tstar is read.  A user-defined temporal covariance (GPCSD_KIND_HOST) has no prior diagonal on the
+ * device: rc -3. */
+int gpcsd_predict_var(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double *z, int nz,
+                      const double *tstar, int ntstar, int type,
+                      double *csd_var_list, double *csd_var, double *lfp_var_list, double *lfp_var);
+/* Same computation (no reference counterpart), results left in the named device buffers "pred_var_csd", "pred_var_lfp" (nz*ntstar)
+ * and "pred_var_csd_list", "pred_var_lfp_list" (n_temporal times that) for gpcsd_fetch / gpcsd_device_buffer.  Waits for its own
+ * work: a numerical failure (rc > 0) is returned by the call itself.  The buffers of the posterior means are left alone. */
+int gpcsd_predict_var_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double *z, int nz,
+                               const double *tstar, int ntstar, int type);
+/* The last product of gpcsd_predict_var alone, on host arrays (no reference counterpart; upload, one launch, download): G (nz, K)
+ * and P (K, C * nts) -- component c in the columns [c * nts, (c + 1) * nts) --, prior_s (nz), kd (C) -> out (C + 1, nz, nts):
+ *   out[c][z][j] = prior_s[z] kd[c]       - sum_k G[z][k] P[k][c * nts + j]^2             c < C
+ *   out[C][z][j] = prior_s[z] sum_c kd[c] - sum_k G[z][k] (sum_c P[k][c * nts + j])^2
+ * P is squared on its way to the multiplier; prior_s kd - sum is one fused multiply-add. */
+int gpcsd_var_contract(gpcsd_ctx *ctx, const double *G, int nz, int K, const double *P, int C, int nts,
+                       const double *prior_s, const double *kd, double *out);
 /* copy `count` doubles of the named ctx-owned device buffer to host; rc -2 if the name is unknown; rc > 0 if the
  * asynchronous gpcsd_predict_resident that produced the buffer failed numerically */
 int gpcsd_fetch(gpcsd_ctx *ctx, const char *name, double *host, long count);
