@@ -77,6 +77,22 @@ class HParamsBatch:
         return ctypes.cast(self.rec.ctypes.data, ctypes.POINTER(HParams))
 
 
+class DebugGemmArgs(ctypes.Structure):
+    """struct gpcsd_debug_gemm_args"""
+    _fields_ = ([(n, ctypes.c_int) for n in ("M", "N", "K", "transA", "transB", "cfg", "epi", "rdiv", "batch", "batch2", "lower",
+                                             "lower_shift")] +
+                [(n, ctypes.c_long) for n in ("lda", "ldb", "ldc", "ldd", "sA", "sB", "sC", "sD", "sColscale", "sKscale", "sA2", "sB2",
+                                              "sC2", "sD2", "sColscale2", "sRowscale2", "sDyn2", "sQuad2", "sKscale2")] +
+                [("alpha", ctypes.c_double), ("A", _c_double_p), ("B", _c_double_p), ("nA", ctypes.c_long), ("nB", ctypes.c_long),
+                 ("C", _c_double_p), ("C2", _c_double_p), ("C3", _c_double_p), ("nC", ctypes.c_long),
+                 ("D", _c_double_p), ("colscale", _c_double_p), ("rowscale", _c_double_p), ("kscale", _c_double_p),
+                 ("nD", ctypes.c_long), ("nColscale", ctypes.c_long), ("nRowscale", ctypes.c_long), ("nKscale", ctypes.c_long),
+                 ("dyn", ctypes.POINTER(ctypes.c_int)), ("nDyn", ctypes.c_long), ("quad_out", _c_double_p), ("nQuad", ctypes.c_long)])
+
+
+EPI_STORE, EPI_DIV_D, EPI_QUAD, EPI_ACCUM, EPI_GRAD, EPI_DUAL_INIT, EPI_SUB = 0, 1, 2, 3, 4, 6, 7      # enum Epi (csrc/kernels.hpp)
+
+
 class HipUnavailable(RuntimeError):
     pass
 
@@ -124,6 +140,7 @@ SIGNATURES = {
     "gpcsd_eigh": (_I, [_P, _DP, _I, _DP, _DP]),
     "gpcsd_eigh_psd": (_I, [_P, _DP, _I, _DP, _DP]),
     "gpcsd_eigh_batch": (_I, [_P, _DP, _I, _I, _DP, _DP, ctypes.POINTER(_I)]),
+    "gpcsd_debug_gemm": (_I, [_P, ctypes.POINTER(DebugGemmArgs)]),
     "gpcsd_eig_D": (_I, [_P, _DP, _I, _DP, _I, _DP, _I, _DP, _DP, _DP]),
     "gpcsd_whitened_quad": (_I, [_P, _DP, _I, _DP, _I, _DP, _DP, _I, _DP]),
     "gpcsd_debug_sytrd": (_I, [_P, _DP, _I, _DP, _DP, _DP, _DP]),
@@ -652,6 +669,54 @@ class Context:
         self._check(self._lib.gpcsd_debug_tridiag_solve(self._h, _ptr(W), _ptr(es), nx, R, nt, *args, float(sig2),
                                                         int(trials_per_pass), _ptr(B)))
         return B
+
+    def debug_gemm(self, M, N, K, A, B, C=None, C2=None, C3=None, D=None, colscale=None, rowscale=None, kscale=None, dyn=None,
+                   quad=None, **desc):
+        """One launch of the fp64 MFMA GEMM core with the whole descriptor in the caller's hands (gpcsd_debug_gemm).  Every operand
+        is a flat float64 array (dyn: ints) that is uploaded exactly as given; C, C2, C3 and quad hold the buffers' initial
+        contents.  desc: the remaining fields of struct gpcsd_debug_gemm_args (transA, lda, cfg, epi, alpha, batch, sA, ...; zero
+        when left out, but alpha, rdiv, batch and batch2 one).  Returns {"C", "C2", "C3", "quad"}: the whole buffers after the
+        launch (None for those not given); the arguments are not written."""
+        a = DebugGemmArgs()
+        a.alpha, a.rdiv, a.batch, a.batch2 = 1.0, 1, 1, 1
+        a.M, a.N, a.K = int(M), int(N), int(K)
+        settable = {n for n, t in DebugGemmArgs._fields_ if t in (ctypes.c_int, ctypes.c_long)} - {"M", "N", "K"}
+        settable = {n for n in settable if not (n[0] == "n" and n[1].isupper())} | {"alpha"}
+        for name, v in desc.items():
+            if name not in settable:
+                raise TypeError("debug_gemm: no descriptor field %r" % name)
+            setattr(a, name, float(v) if name == "alpha" else int(v))
+        keep = {}
+
+        def flat(x, copy):
+            if x is None:
+                return None
+            x = np.asarray(x, dtype=np.float64)
+            if x.ndim != 1:
+                raise ValueError("debug_gemm takes flat arrays")
+            return np.array(x, copy=True) if copy else np.ascontiguousarray(x)
+
+        for name, x, nfield, copy in (("A", A, "nA", False), ("B", B, "nB", False), ("C", C, "nC", True), ("D", D, "nD", False),
+                                      ("colscale", colscale, "nColscale", False), ("rowscale", rowscale, "nRowscale", False),
+                                      ("kscale", kscale, "nKscale", False), ("quad_out", quad, "nQuad", True)):
+            x = flat(x, copy)
+            keep[name] = x
+            if x is not None:
+                setattr(a, name, _ptr(x))
+                setattr(a, nfield, x.size)
+        for name, x in (("C2", C2), ("C3", C3)):
+            x = flat(x, True)
+            keep[name] = x
+            if x is not None:
+                if keep["C"] is None or x.size != keep["C"].size:
+                    raise ValueError("debug_gemm: %s must have C's length" % name)
+                setattr(a, name, _ptr(x))
+        if dyn is not None:
+            keep["dyn"] = np.ascontiguousarray(dyn, dtype=np.int32).reshape(-1)
+            a.dyn = keep["dyn"].ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+            a.nDyn = keep["dyn"].size
+        self._check(self._lib.gpcsd_debug_gemm(self._h, ctypes.byref(a)))
+        return {"C": keep["C"], "C2": keep["C2"], "C3": keep["C3"], "quad": keep["quad_out"]}
 
     def eig_D(self, Ks, Kt, sig2n):
         Ks, Kt = _arr(Ks), _arr(Kt)

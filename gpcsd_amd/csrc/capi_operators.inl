@@ -337,6 +337,92 @@ extern "C" int gpcsd_debug_tridiag_solve(gpcsd_ctx *c, const double *W, const do
     GP_API_END(c)
 }
 
+// diagnostics: one launch of the fp64 MFMA GEMM core (gemm_f64.hip) with the whole GemmDesc in the caller's hands, host arrays in
+// and out.  Plumbing around gemm_f64: every operand's reach is checked against its length before anything is uploaded.
+extern "C" int gpcsd_debug_gemm(gpcsd_ctx *c, gpcsd_debug_gemm_args *a) {
+    GP_API_BEGIN(c)
+    GP_REQUIRE(a && a->A && a->B, -3, "debug_gemm: bad arguments");
+    GP_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0, -3, "debug_gemm: empty problem %dx%dx%d", a->M, a->N, a->K);
+    GP_REQUIRE(a->batch >= 1 && a->batch2 >= 1 && (long)a->batch * a->batch2 <= 65535, -3, "debug_gemm: bad batch counts %d x %d",
+               a->batch, a->batch2);
+    GP_REQUIRE(a->rdiv >= 1 && a->lower_shift >= 0, -3, "debug_gemm: bad rdiv or lower_shift");
+    const int epi = a->epi;
+    const bool uses_D = epi == EPI_DIV_D || epi == EPI_QUAD || epi == EPI_GRAD;
+    const bool sums = epi == EPI_QUAD || epi == EPI_GRAD;
+    const long LD_MAX = 1L << 31, S_MAX = 1L << 40;          // (the reaches below stay far inside 64 bits)
+    // reach of an operand of `rows` rows of `cols` elements, ld apart, over both batch levels; -1: not addressable as described
+    auto reach = [&](long rows, long cols, long ld, long s1, long s2) -> long {
+        if (ld < cols || ld >= LD_MAX || s1 < 0 || s2 < 0 || s1 >= S_MAX || s2 >= S_MAX) return -1;
+        return (rows - 1) * ld + cols + (a->batch - 1) * s1 + (a->batch2 - 1) * s2;
+    };
+    auto fits = [](long need, long have) { return need >= 0 && need <= have; };
+    const long M = a->M, N = a->N, K = a->K, rowsD = (M - 1) / a->rdiv + 1;
+    GP_REQUIRE(fits(a->transA ? reach(K, M, a->lda, a->sA, a->sA2) : reach(M, K, a->lda, a->sA, a->sA2), a->nA), -3,
+               "debug_gemm: A (lda %ld, strides %ld, %ld) reaches past its %ld elements", a->lda, a->sA, a->sA2, a->nA);
+    GP_REQUIRE(fits(a->transB ? reach(N, K, a->ldb, a->sB, a->sB2) : reach(K, N, a->ldb, a->sB, a->sB2), a->nB), -3,
+               "debug_gemm: B (ldb %ld, strides %ld, %ld) reaches past its %ld elements", a->ldb, a->sB, a->sB2, a->nB);
+    if (epi != EPI_QUAD || a->C)
+        GP_REQUIRE(a->C && fits(reach(M, N, a->ldc, a->sC, a->sC2), a->nC), -3,
+                   "debug_gemm: C (ldc %ld, strides %ld, %ld) reaches past its %ld elements", a->ldc, a->sC, a->sC2, a->nC);
+    GP_REQUIRE((!a->C2 && !a->C3) || a->C, -3, "debug_gemm: C2 / C3 without C");
+    if (uses_D)
+        GP_REQUIRE(a->D && fits(reach(rowsD, N, a->ldd, a->sD, a->sD2), a->nD), -3,
+                   "debug_gemm: D (ldd %ld, strides %ld, %ld) reaches past its %ld elements", a->ldd, a->sD, a->sD2, a->nD);
+    if (a->colscale || (epi == EPI_GRAD && a->C2))
+        GP_REQUIRE(a->colscale && fits(reach(1, N, N, a->sColscale, a->sColscale2), a->nColscale), -3,
+                   "debug_gemm: colscale reaches past its %ld elements", a->nColscale);
+    if (a->rowscale || epi == EPI_GRAD)
+        GP_REQUIRE(a->rowscale && fits(reach(1, rowsD, rowsD, 0, a->sRowscale2), a->nRowscale), -3,
+                   "debug_gemm: rowscale reaches past its %ld elements", a->nRowscale);
+    if (a->kscale)
+        GP_REQUIRE(fits(reach(1, K, K, a->sKscale, a->sKscale2), a->nKscale), -3, "debug_gemm: kscale reaches past its %ld elements",
+                   a->nKscale);
+    if (sums)
+        GP_REQUIRE(a->quad_out && a->sQuad2 >= 0 && a->sQuad2 < S_MAX &&
+                       (epi == EPI_GRAD ? 2 : 1) + (a->batch2 - 1) * a->sQuad2 <= a->nQuad,
+                   -3, "debug_gemm: quad_out reaches past its %ld elements", a->nQuad);
+    if (a->dyn) {
+        GP_REQUIRE(fits(reach(1, a->batch, a->batch, 0, a->sDyn2), a->nDyn), -3, "debug_gemm: dyn reaches past its %ld entries", a->nDyn);
+        for (int z2 = 0; z2 < a->batch2; ++z2)
+            for (int z1 = 0; z1 < a->batch; ++z1) {
+                const int d = a->dyn[z2 * a->sDyn2 + z1];
+                GP_REQUIRE(d >= 0 && d <= a->N && d <= a->K, -3, "debug_gemm: dyn = %d outside [0, min(N, K)]", d);
+            }
+    }
+    if (int rc = dbg_tri_idle(c)) return rc;               // gemm_partials is the fused path's scratch
+    GemmDesc g;
+    g.M = a->M; g.N = a->N; g.K = a->K;
+    g.A = c->upload<double>("dbg_gemm_A", a->A, (size_t)a->nA); g.lda = a->lda; g.transA = a->transA != 0;
+    g.B = c->upload<double>("dbg_gemm_B", a->B, (size_t)a->nB); g.ldb = a->ldb; g.transB = a->transB != 0;
+    if (a->C) g.C = c->upload<double>("dbg_gemm_C", a->C, (size_t)a->nC);
+    if (a->C2) g.C2 = c->upload<double>("dbg_gemm_C2", a->C2, (size_t)a->nC);
+    if (a->C3) g.C3 = c->upload<double>("dbg_gemm_C3", a->C3, (size_t)a->nC);
+    g.ldc = a->ldc;
+    if (uses_D) g.D = c->upload<double>("dbg_gemm_D", a->D, (size_t)a->nD);
+    g.rdiv = a->rdiv; g.ldd = a->ldd; g.sD = a->sD;
+    if (a->colscale) g.colscale = c->upload<double>("dbg_gemm_colscale", a->colscale, (size_t)a->nColscale);
+    if (a->rowscale) g.rowscale = c->upload<double>("dbg_gemm_rowscale", a->rowscale, (size_t)a->nRowscale);
+    if (a->kscale) g.kscale = c->upload<double>("dbg_gemm_kscale", a->kscale, (size_t)a->nKscale);
+    g.sColscale = a->sColscale; g.sKscale = a->sKscale; g.sKscale2 = a->sKscale2;
+    g.batch = a->batch; g.sA = a->sA; g.sB = a->sB; g.sC = a->sC;
+    g.batch2 = a->batch2; g.sA2 = a->sA2; g.sB2 = a->sB2; g.sC2 = a->sC2; g.sD2 = a->sD2;
+    g.sColscale2 = a->sColscale2; g.sRowscale2 = a->sRowscale2; g.sDyn2 = a->sDyn2; g.sQuad2 = a->sQuad2;
+    g.alpha = a->alpha; g.epi = epi; g.cfg = a->cfg;
+    double *dq = nullptr;
+    if (sums) g.quad_out = dq = c->upload<double>("dbg_gemm_quad", a->quad_out, (size_t)a->nQuad);
+    if (a->dyn) g.dyn = c->upload<int>("dbg_gemm_dyn", a->dyn, (size_t)a->nDyn);
+    g.lower = a->lower != 0; g.lower_shift = a->lower_shift;
+    g.prof_name = "gemm_debug";
+    gemm_f64(c, g, c->stream);
+    if (a->C) c->download(a->C, g.C, (size_t)a->nC * sizeof(double));
+    if (a->C2) c->download(a->C2, g.C2, (size_t)a->nC * sizeof(double));
+    if (a->C3) c->download(a->C3, g.C3, (size_t)a->nC * sizeof(double));
+    if (dq) c->download(a->quad_out, dq, (size_t)a->nQuad * sizeof(double));
+    c->sync();
+    return 0;
+    GP_API_END(c)
+}
+
 extern "C" int gpcsd_eig_D(gpcsd_ctx *c, const double *Ks, int nx, const double *Kt, int nt, const double *sig2n, int n_sig,
                            double *Qs, double *Qt, double *Dvec) {
     GP_API_BEGIN(c)
@@ -484,7 +570,7 @@ __global__ void fill_pattern_kernel(double *p, long n, double a) {
 }
 
 // Time the fp64 MFMA GEMM on device-resident pseudo-random operands: average ms per launch over `reps` launches.
-// cfg = 0 picks the tile configuration automatically, 1..6 forces one (tuning aid; see gemm_f64.hip).
+// cfg = 0 picks the tile configuration automatically, 1, 2, 3 or 5 forces one (tuning aid; see gemm_f64.hip).
 extern "C" int gpcsd_gemm_bench(gpcsd_ctx *c, int transA, int transB, int M, int N, int K, int cfg, int reps, double *ms_out) {
     GP_API_BEGIN(c)
     GP_REQUIRE(M > 0 && N > 0 && K > 0 && reps > 0 && ms_out, -3, "gemm_bench: bad arguments");

@@ -12,7 +12,8 @@ enum Epi : int {
     EPI_QUAD = 2,    // no store; partial sums of acc^2 * D[...] (reciprocals; deterministic two-stage reduce)
     EPI_ACCUM = 3,   // C += alpha * acc
     EPI_GRAD = 4,    // b = acc * D (reciprocals): C = b, C2 = b*colscale[col], C3 = b*rowscale[row/rdiv]; sums of acc*b and b*b
-    EPI_DUAL_INIT = 6, // C = alpha*acc and C2 = alpha*acc (first term of a running sum: no read, no zero fill)
+    EPI_DUAL_INIT = 6, // C = alpha*acc and C2 = alpha*acc (first term of a running sum).  NOT instantiated any more (dropped with the
+                       // other unused variants): gemm_f64 refuses it with -3; the number stays reserved
     EPI_SUB = 7        // C = C - acc with C read at the START of the tile (accumulators initialised to -C, plain-store epilogue with
                        // alpha = -1): the rank-k trailing updates of the Cholesky -- EPI_ACCUM's read-modify-write sits at the end
                        // of a tile, where nothing hides its latency.  A (M,K) row-major, B stored (N,K) only.

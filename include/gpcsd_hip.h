@@ -186,6 +186,33 @@ int gpcsd_debug_tridiag_solve(gpcsd_ctx *ctx, const double *W, const double *es,
                               const double *d0, const double *e0, double m0, int np0, int c00,
                               const double *d1, const double *e1, double m1, int np1, int c01,
                               double sig2, int pass, double *B);
+/* Diagnostics for the fp64 MFMA GEMM core (no reference counterpart): one launch of the core with the whole descriptor in the
+ * caller's hands.  The fields mirror GemmDesc (csrc/kernels.hpp: layouts, epilogues, both batch levels, dyn, lower); every
+ * operand is a host array with its length in doubles (ints for dyn) and is uploaded exactly as given.  C, C2, C3 and quad_out
+ * are in/out: their contents are the buffers' initial contents and come back whole, padding included.  The furthest element
+ * every operand can address is computed from the sizes, strides and batch counts and compared with its length before
+ * anything is uploaded: -3 for an operand that is missing, too short or laid out below the minimum leading dimension. */
+typedef struct gpcsd_debug_gemm_args {
+    int M, N, K, transA, transB;
+    int cfg, epi;                        /* cfg 0 (automatic), 1, 2, 3, 5; epi: enum Epi */
+    int rdiv, batch, batch2;
+    int lower, lower_shift;
+    long lda, ldb, ldc, ldd;
+    long sA, sB, sC, sD, sColscale, sKscale;                                  /* strides of the inner batch level */
+    long sA2, sB2, sC2, sD2, sColscale2, sRowscale2, sDyn2, sQuad2, sKscale2; /* ... of the outer one */
+    double alpha;
+    const double *A, *B;
+    long nA, nB;
+    double *C, *C2, *C3;                 /* C2 / C3 (EPI_GRAD, optional) have C's length and layout */
+    long nC;
+    const double *D, *colscale, *rowscale, *kscale;
+    long nD, nColscale, nRowscale, nKscale;
+    const int *dyn;                      /* optional: effective N = K of batch entry (z2, z1) at dyn[z2 * sDyn2 + z1] */
+    long nDyn;
+    double *quad_out;                    /* EPI_QUAD: one sum per outer entry at z2 * sQuad2, EPI_GRAD: two */
+    long nQuad;
+} gpcsd_debug_gemm_args;
+int gpcsd_debug_gemm(gpcsd_ctx *ctx, gpcsd_debug_gemm_args *args);
 /* comp_eig_D(Ks, Kt, sig2n)            utility_functions.py:44-64 ; Dvec has nx*nt entries */
 int gpcsd_eig_D(gpcsd_ctx *ctx, const double *Ks, int nx, const double *Kt, int nt,
                 const double *sig2n, int n_sig, double *Qs, double *Qt, double *Dvec);
@@ -504,7 +531,7 @@ int gpcsd_prof_names(gpcsd_ctx *ctx, char *buf, int buflen);
 /* back-to-back v_mfma_f64_16x16x4_f64 microbenchmark: measured TFLOP/s */
 int gpcsd_mfma_f64_peak(gpcsd_ctx *ctx, double *tflops);
 /* average ms per launch of the fp64 MFMA GEMM on device-resident pseudo-random operands; cfg 0 = automatic tile
- * configuration, 1..6 = forced (tuning aid) */
+ * configuration, 1, 2, 3 or 5 = forced (tuning aid) */
 int gpcsd_gemm_bench(gpcsd_ctx *ctx, int transA, int transB, int M, int N, int K, int cfg, int reps, double *ms_out);
 /* average ms of the blocked Cholesky (numpy.linalg.cholesky of gpcsd1d.py:303-304 / gpcsd2d.py:343-350; the dense cross-check's
  * factor at N = nx * nt) on a device-resident, device-generated SPD test matrix of order n; events on the call's own stream
