@@ -168,6 +168,9 @@ SIGNATURES = {
     "gpcsd_predict_var": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _DP, _DP, _DP, _DP]),
     "gpcsd_predict_var_resident": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I]),
     "gpcsd_var_contract": (_I, [_P, _DP, _I, _I, _DP, _I, _I, _DP, _DP, _DP]),
+    "gpcsd_loo": (_I, [_P, ctypes.POINTER(HParams), _DP, _DP, _DP, _DP]),
+    "gpcsd_loo_resident": (_I, [_P, ctypes.POINTER(HParams), _I]),
+    "gpcsd_loo_contract": (_I, [_P, _DP, _DP, _DP, _DP, _I, _I, _I, _I, _DP, _DP, _DP]),
     "gpcsd_fetch": (_I, [_P, ctypes.c_char_p, _DP, _L]),
     "gpcsd_device_buffer": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
     "gpcsd_sample_prior": (_I, [_P, ctypes.POINTER(HParams), _I, _DP, _I, _DP]),
@@ -928,6 +931,33 @@ class Context:
         out = np.empty((C + 1, nz, nts))
         self._check(self._lib.gpcsd_var_contract(self._h, _ptr(G), nz, K, _ptr(P), int(C), nts, _ptr(prior_s), _ptr(kd), _ptr(out)))
         return out
+
+    def loo(self, hp, shape, want_mean=True):
+        """Leave-one-out scores (gpcsd_loo) as host arrays; shape = (nx, nt, ntrials) of the resident data.  Dict with "var" (nx, nt),
+        "lpd" and "sse" (nx, ntrials) and "mean" (nx, nt, ntrials) or None."""
+        nx, nt, R = (int(v) for v in shape)
+        res = {"var": np.empty((nx, nt)), "lpd": np.empty((nx, R)), "sse": np.empty((nx, R)),
+               "mean": pinned_pool.empty((nx, nt, R)) if want_mean else None}
+        self._check(self._lib.gpcsd_loo(self._h, ctypes.byref(hp), _ptr(res["var"]), _ptr(res["mean"]), _ptr(res["lpd"]), _ptr(res["sse"])))
+        return res
+
+    def loo_resident(self, hp, want_mean=True):
+        """The same into the device buffers "loo_var", "loo_lpd", "loo_sse" (and "loo_mean") only; read back with fetch()."""
+        self._check(self._lib.gpcsd_loo_resident(self._h, ctypes.byref(hp), int(bool(want_mean))))
+
+    def loo_contract(self, V, Qt, c, Y, R, want_mean=True):
+        """The last product of loo() alone (gpcsd_loo_contract): V (nx * R, K), Qt (nt, K), c (nx, nt), Y (nx * R, nt) ->
+        (mean (nx, nt, R) or None, lpd (nx, R), sse (nx, R))."""
+        V, Qt, c, Y = _arr(V), _arr(Qt), _arr(c), _arr(Y)
+        nx, nt = c.shape
+        K = Qt.shape[1]
+        if V.shape != (nx * R, K) or Qt.shape[0] != nt or Y.shape != (nx * R, nt):
+            raise ValueError("loo_contract: V (nx * R, K), Qt (nt, K), c (nx, nt), Y (nx * R, nt)")
+        mean = np.empty((nx, nt, R)) if want_mean else None
+        lpd, sse = np.empty((nx, R)), np.empty((nx, R))
+        self._check(self._lib.gpcsd_loo_contract(self._h, _ptr(V), _ptr(Qt), _ptr(c), _ptr(Y), nx, int(R), nt, K, _ptr(mean), _ptr(lpd),
+                                                 _ptr(sse)))
+        return mean, lpd, sse
 
     def fetch(self, name, shape):
         out = pinned_pool.empty(shape)

@@ -752,27 +752,36 @@ static void pred_cross_front(gpcsd_ctx *c, const gpcsd_hparams *hp, EigState &e,
         temporal_cross_gram(c, hp, cc, dts, ntstar, t, nt, f.Kts + (size_t)cc * ntstar * nt, s);
     join_temporal(c, e, nullptr, false);      // predict never reads sum(log D)
 }
-static PredFullFront predict_full_front(gpcsd_ctx *c, const gpcsd_hparams *hp, EigState &e, const double *z, int nz, const double *tstar,
-                                        int ntstar, int type) {
-    const int nx = c->nx, nt = c->nt, R = c->ntrials;
-    const long RT = (long)R * nt;
-    hipStream_t s = c->stream;
-    double *W = c->buf<double>("proj_W", (size_t)nx * RT);
-    PredFullFront f;
-    f.Bm = c->buf<double>("pred_B", (size_t)nx * RT);
+// The part of it that reads the trials and neither sites nor times (all the leave-one-out scores need), in two steps because the
+// second one needs the joined temporal side: W = Qs^T Y (spatial side only), then Bm = (W Qt) / D.
+static void pred_data_spatial(gpcsd_ctx *c, EigState &e, double *W) {
+    const int nx = c->nx;
+    const long RT = (long)c->ntrials * c->nt;
     GemmDesc g1;                          // W = Qs^T Y
     g1.M = nx; g1.N = (int)RT; g1.K = nx;
     g1.A = e.Qs; g1.lda = nx; g1.transA = true;
     g1.B = c->d_lfp; g1.ldb = RT; g1.C = W; g1.ldc = RT;
     g1.prof_name = "gemm_proj_spatial";
-    gemm_f64(c, g1, s);
-    pred_cross_front(c, hp, e, z, nz, tstar, ntstar, type, f);
+    gemm_f64(c, g1, c->stream);
+}
+static void pred_data_temporal(gpcsd_ctx *c, EigState &e, const double *W, double *Bm) {
+    const int nx = c->nx, nt = c->nt, R = c->ntrials;
     GemmDesc g2;                          // Bm = (W Qt) / D
     g2.M = nx * R; g2.N = nt; g2.K = nt;
-    g2.A = W; g2.lda = nt; g2.B = e.Qt; g2.ldb = nt; g2.C = f.Bm; g2.ldc = nt;
+    g2.A = W; g2.lda = nt; g2.B = e.Qt; g2.ldb = nt; g2.C = Bm; g2.ldc = nt;
     g2.epi = EPI_DIV_D; g2.D = e.Dinv; g2.rdiv = R; g2.ldd = nt;
     g2.prof_name = "gemm_pred_temporal_div";
-    gemm_f64(c, g2, s);
+    gemm_f64(c, g2, c->stream);
+}
+static PredFullFront predict_full_front(gpcsd_ctx *c, const gpcsd_hparams *hp, EigState &e, const double *z, int nz, const double *tstar,
+                                        int ntstar, int type) {
+    const long RT = (long)c->ntrials * c->nt;
+    double *W = c->buf<double>("proj_W", (size_t)c->nx * RT);
+    PredFullFront f;
+    f.Bm = c->buf<double>("pred_B", (size_t)c->nx * RT);
+    pred_data_spatial(c, e, W);
+    pred_cross_front(c, hp, e, z, nz, tstar, ntstar, type, f);
+    pred_data_temporal(c, e, W, f.Bm);
     return f;
 }
 
@@ -1356,6 +1365,84 @@ extern "C" int gpcsd_predict_var(gpcsd_ctx *c, const gpcsd_hparams *hp, const do
         if (list[w])
             c->download(list[w], c->bufs[w ? "pred_var_lfp_list" : "pred_var_csd_list"].p, out_elems * hp->n_temporal * sizeof(double));
     }
+    c->sync();
+    return rc;
+    GP_API_END(c)
+}
+
+// Leave-one-out predictive mean, variance and log score of every training sample (gpcsd_loo; no reference counterpart), of the
+// model whose log-likelihood gpcsd_loglik returns: K = (Qs (x) Qt) diag(D) (Qs (x) Qt)^T exactly as front_half(c, hp, hp->jitter)
+// builds it (the jitter on Ks, a noise list on the eigen-index).  With c = diag(K^-1) and beta_r = K^-1 y_r (Rasmussen & Williams
+// 5.4.2) the score of sample (x, t) of trial r needs no refit:
+//   c[x][t] = sum_{x',i'} Qs[x][x']^2 Qt[t][i']^2 / D[x'][i']          two squared-operand products, every term >= 0
+//   beta_r  = Qs ((Qs^T Y_r Qt) / D) Qt^T                               the prediction front's Bm, V = Qs Bm, then gemm_loo
+// in the merged (unfolded, eigenvector) basis, which is correct for every model the library accepts.  Outputs: loo_var (nx, nt),
+// loo_lpd / loo_sse (nx, R), loo_mean (nx, nt, R) when asked.
+static int loo_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, bool want_mean) {
+    GP_REQUIRE(hp != nullptr, -3, "null hparams");
+    GP_REQUIRE(c->d_lfp != nullptr, -4, "lfp not set (call gpcsd_set_lfp)");
+    const int nx = c->nx, nt = c->nt, R = c->ntrials;
+    const long RT = (long)R * nt, nrow = (long)nx * R;
+    // (checked before anything is read: one row of the projected data is a flat GEMM operand row)
+    GP_REQUIRE(RT < GPCSD_MAX_GEMM_LD_KMAJOR && nrow < (1L << 31), GPCSD_ERR_CAPACITY,
+               "loo: ntrials * nt = %ld (or nx * ntrials = %ld) exceeds the capacity of one operand row (%ld doubles; "
+               "GPCSD_MAX_GEMM_LD_KMAJOR)", RT, nrow, (long)GPCSD_MAX_GEMM_LD_KMAJOR);
+    // the scratch of the prediction calls is rewritten below: whatever an earlier queued prediction still owes is collected first
+    if (int rc = drain_async(c)) return rc;
+    EigState e = front_half(c, hp, hp->jitter);    // the jitter of loglik (gpcsd1d.py:117)
+    hipStream_t s = c->stream;
+    double *W = c->buf<double>("proj_W", (size_t)nx * RT);
+    double *Bm = c->buf<double>("pred_B", (size_t)nx * RT);
+    double *V = c->buf<double>("loo_V", (size_t)nx * RT);
+    double *H = c->buf<double>("loo_H", (size_t)nx * nt);
+    double *QtT = c->buf<double>("loo_QtT", (size_t)nt * nt);
+    double *cdiag = c->buf<double>("loo_c", (size_t)nx * nt);
+    double *var = c->buf<double>("loo_var", (size_t)nx * nt);
+    double *lpd = c->buf<double>("loo_lpd", (size_t)nrow), *sse = c->buf<double>("loo_sse", (size_t)nrow);
+    double *mean = want_mean ? c->buf<double>("loo_mean", (size_t)nx * RT) : nullptr;
+    pred_data_spatial(c, e, W);
+    join_temporal(c, e, nullptr, false);           // nobody reads sum(log D) here
+    VarDesc v1;                           // H[x][i'] = sum_x' Qs[x][x']^2 Dinv[x'][i']
+    v1.A = e.Qs; v1.lda = nx; v1.B = e.Dinv; v1.ldb = nt;
+    v1.nrow = nx; v1.ncol = nt; v1.K = nx; v1.sq_a = true; v1.list = H;
+    v1.prof_name = "gemm_var_H";
+    gemm_var(c, v1, s);
+    k_swap_last2(c, e.Qt, QtT, 1, nt, nt, s);      // the eigen-index leading: the squared operand's layout
+    VarDesc v2;                           // c[x][t] = sum_i' H[x][i'] Qt[t][i']^2
+    v2.A = H; v2.lda = nt; v2.B = QtT; v2.ldb = nt;
+    v2.nrow = nx; v2.ncol = nt; v2.K = nt; v2.list = cdiag;
+    v2.prof_name = "gemm_var_c";
+    gemm_var(c, v2, s);
+    k_loo_var(c, cdiag, var, (long)nx * nt, s);
+    pred_data_temporal(c, e, W, Bm);
+    GemmDesc g3;                          // V[x][(r,i')] = sum_x' Qs[x][x'] Bm[x'][(r,i')]
+    g3.M = nx; g3.N = (int)RT; g3.K = nx;
+    g3.A = e.Qs; g3.lda = nx; g3.B = Bm; g3.ldb = RT; g3.C = V; g3.ldc = RT;
+    g3.prof_name = "gemm_loo_V";
+    gemm_f64(c, g3, s);
+    LooDesc l;                            // beta[(x,r)][t] = sum_i' V[(x,r)][i'] Qt[t][i'], and everything behind it
+    l.V = V; l.ldv = nt; l.Qt = e.Qt; l.ldq = nt; l.c = cdiag; l.y = c->d_lfp;
+    l.K = nt; l.nt = nt; l.R = R; l.nrow = nrow;
+    l.mean = mean; l.lpd = lpd; l.sse = sse;
+    gemm_loo(c, l, s);
+    return finish_call(c, e, nullptr, 0);
+}
+
+extern "C" int gpcsd_loo_resident(gpcsd_ctx *c, const gpcsd_hparams *hp, int want_mean) {
+    GP_API_BEGIN(c)
+    return loo_impl(c, hp, want_mean != 0);
+    GP_API_END(c)
+}
+
+extern "C" int gpcsd_loo(gpcsd_ctx *c, const gpcsd_hparams *hp, double *var, double *mean, double *lpd, double *sse) {
+    GP_API_BEGIN(c)
+    const int rc = loo_impl(c, hp, mean != nullptr);
+    if (rc < 0) return rc;
+    const size_t nxt = (size_t)c->nx * c->nt, nrow = (size_t)c->nx * c->ntrials;
+    if (var) c->download(var, c->bufs["loo_var"].p, nxt * sizeof(double));
+    if (mean) c->download(mean, c->bufs["loo_mean"].p, nxt * c->ntrials * sizeof(double));
+    if (lpd) c->download(lpd, c->bufs["loo_lpd"].p, nrow * sizeof(double));
+    if (sse) c->download(sse, c->bufs["loo_sse"].p, nrow * sizeof(double));
     c->sync();
     return rc;
     GP_API_END(c)

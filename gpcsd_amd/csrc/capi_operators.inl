@@ -561,6 +561,36 @@ extern "C" int gpcsd_var_contract(gpcsd_ctx *c, const double *G, int nz, int K, 
     GP_API_END(c)
 }
 
+// The last product of gpcsd_loo alone, on host arrays (no reference counterpart; gemm_f64.hip: gemm_loo_kernel): V (nx * R, K),
+// Qt (nt, K), cdiag (nx, nt) > 0, Y (nx * R, nt) -> mean (nx, nt, R) (may be NULL), lpd and sse (nx * R).
+extern "C" int gpcsd_loo_contract(gpcsd_ctx *c, const double *V, const double *Qt, const double *cdiag, const double *Y, int nx, int R,
+                                  int nt, int K, double *mean, double *lpd, double *sse) {
+    GP_API_BEGIN(c)
+    GP_REQUIRE(V && Qt && cdiag && Y && lpd && sse && nx > 0 && R > 0 && nt > 0 && K > 0, -3, "loo_contract: bad arguments");
+    // (checked before anything is read)
+    GP_REQUIRE((long)R * nt < GPCSD_MAX_GEMM_LD_KMAJOR && (long)nx * R < (1L << 31) && K < (1 << 22), GPCSD_ERR_CAPACITY,
+               "loo_contract: R * nt = %ld (or nx * R = %ld, or K = %d) exceeds the capacity of one operand row", (long)R * nt,
+               (long)nx * R, K);
+    const size_t nrow = (size_t)nx * R;
+    LooDesc l;
+    l.V = c->upload<double>("op_in0", V, nrow * K); l.ldv = K;
+    l.Qt = c->upload<double>("op_in1", Qt, (size_t)nt * K); l.ldq = K;
+    l.c = c->upload<double>("op_in2", cdiag, (size_t)nx * nt);
+    l.y = c->upload<double>("op_in3", Y, nrow * nt);
+    l.K = K; l.nt = nt; l.R = R; l.nrow = (long)nrow;
+    double *dO = c->buf<double>("op_out", nrow * nt + 2 * nrow);
+    l.mean = mean ? dO + 2 * nrow : nullptr;
+    l.lpd = dO; l.sse = dO + nrow;
+    gemm_loo(c, l, c->stream);
+    c->download(lpd, l.lpd, nrow * sizeof(double));
+    c->download(sse, l.sse, nrow * sizeof(double));
+    if (mean) c->download(mean, l.mean, nrow * nt * sizeof(double));
+    c->sync();
+    if (c->prof_mode == 1) c->prof_collect();
+    return 0;
+    GP_API_END(c)
+}
+
 __global__ void fill_pattern_kernel(double *p, long n, double a) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         unsigned long long h = (unsigned long long)i * 6364136223846793005ull + 1442695040888963407ull;

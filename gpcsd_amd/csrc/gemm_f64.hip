@@ -1233,6 +1233,266 @@ void gemm_var(gpcsd_ctx *c, const VarDesc &d, hipStream_t s) {
     GP_HIP(hipGetLastError());
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Last product of the leave-one-out scores (gpcsd_loo), LooDesc in kernels.hpp:
+//
+//   beta[(x, r)][t] = sum_i' V[(x, r)][i'] Qt[t][i']  ( = K^-1 y_r at sample (x, t))         never stored
+//   e = beta / c[x][t],   mean[x][t][r] = y[(x, r)][t] - e,
+//   lpd[(x, r)] = sum_t 1/2 log c - 1/2 beta e - 1/2 log 2 pi,    sse[(x, r)] = sum_t e^2
+//
+// As gemm_pred_at_kernel the kernel computes the transposed product, rows = t, columns = (x, r), so that the lanes of a wave run
+// along r, the innermost index of `mean`, and every store instruction writes 16 consecutive trials of four times.  A workgroup
+// owns a 64 x 64 tile, four waves of 2 x 2 fragments.  The sums over t of a column: a lane adds its eight elements per column
+// fragment in index order, the four lane groups of the wave (the rows fq + 4 r of a fragment) meet through two exchanges whose
+// additions are commutative -- every lane ends with the same bits --, the two waves that share the columns (the tile's two time
+// halves) through LDS, and the tile writes ONE partial per column and quantity to partials[quantity][time tile][column];
+// loo_reduce_kernel adds the time tiles in index order.  No atomics: the same call gives the same bits every time.
+// Edges as the sibling kernels: a time or column past the end reads the last valid one, and its accumulators are neither stored
+// nor summed; the last K tile is zero-masked in LDS.
+struct LooK {
+    const double *V;             // [(x, r)][K] row-major
+    long ldv;
+    const double *Qt;            // [nt][K] row-major
+    long ldq;
+    const double *c;             // [nx][nt]
+    const double *y;             // [(x, r)][nt]
+    int K, nt, R;
+    long nrow;                   // nx * R
+    double *mean;                // [x][t][r] (nullptr: scores only)
+    double *partials;            // [2][tiles_t][nrow]
+    int tiles_t;
+};
+
+__global__ __launch_bounds__(256) void gemm_loo_kernel(LooK g) {
+    constexpr int NT = 256, BK = 16, BM = 64, BN = 64;
+    using TileA = Tile<BM, false, NT, BK>;    // Qt: global [rows t][K]
+    using TileB = Tile<BN, false, NT, BK>;    // V: global [cols (x, r)][K]
+    __shared__ double lds[2 * (TileA::LDS_ELEMS + TileB::LDS_ELEMS)];
+    __shared__ double wsum[2][2][BN];         // [quantity][time half of the tile][column]
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wr = wid >> 1, wc = wid & 1;
+    // XCD-aware order as in gemm_f64_kernel: consecutive logical tiles share the V panel (the long dimension)
+    int L = blockIdx.x;
+    {
+        const int total = gridDim.x;
+        if (total >= 64) {
+            const int x = L & 7, q = total >> 3, r = total & 7;
+            L = x * q + (x < r ? x : r) + (L >> 3);
+        }
+    }
+    const int tile_t = L % g.tiles_t;
+    const long tile_c = L / g.tiles_t;
+    const int t0 = tile_t * BM;
+    const long n0 = tile_c * BN;
+    const int fr = lane & 15, fq = lane >> 4;
+
+    d4 acc[2][2];                                              // [time fragment][column fragment]
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
+
+    int oa0, ka0, ob0, kb0;
+    TileA::slot0(tid, oa0, ka0);
+    TileB::slot0(tid, ob0, kb0);
+    double *const swA = lds + TileA::lds_index(oa0, ka0);
+    double *const swB = lds + 2 * TileA::LDS_ELEMS + TileB::lds_index(ob0, kb0);
+    using Buf0 = std::integral_constant<int, 0>;
+    using Buf1 = std::integral_constant<int, 1>;
+
+    const int K = g.K;
+    unsigned offA[TileA::PER_THREAD], offB[TileB::PER_THREAD];
+    TileA::setup(offA, g.ldq, t0, g.nt, tid);
+    int relB[TileB::PER_THREAD];
+#pragma unroll
+    for (int i = 0; i < TileB::PER_THREAD; ++i) {
+        const long col = n0 + ob0 + TileB::DO * i;
+        relB[i] = (int)((col < g.nrow ? col : g.nrow - 1) - n0);
+        offB[i] = (unsigned)(((long)relB[i] * g.ldv + kb0) * 8);
+    }
+    const double *const baseA = TileA::tile_base(g.Qt, g.ldq, t0);     // wave-uniform; 32-bit offsets span one 64-row tile only
+    const double *const baseB = g.V + n0 * g.ldv;
+    const int nk = (K + BK - 1) / BK, nfull = K / BK;
+    double ra[TileA::PER_THREAD], rb[TileB::PER_THREAD];
+    const double *const srA = lds + TileA::lds_index(wr * 16 + fr, fq);
+    const double *const srB = lds + 2 * TileA::LDS_ELEMS + TileB::lds_index(wc * 16 + fr, fq);
+
+    auto load_full = [&](int t) {
+        TileA::gload(ra, TileA::rsrc(baseA, g.ldq, t), 0, offA);
+        TileB::gload(rb, TileB::rsrc(baseB, g.ldv, t), 0, offB);
+    };
+    auto load_any = [&](int t) {
+        if (t < nfull) {
+            load_full(t);
+        } else {                                               // partial K tile: out-of-range k reads the last valid one
+            const int kleft = K - t * BK;
+            TileA::gload_tail(ra, TileA::rsrc(baseA, g.ldq, t), 0, g.ldq, t0, g.nt, kleft, tid);
+            const __amdgpu_buffer_rsrc_t rsb = TileB::rsrc(baseB, g.ldv, t);
+            const int kc = kb0 < kleft ? kb0 : kleft - 1;
+#pragma unroll
+            for (int i = 0; i < TileB::PER_THREAD; ++i) rb[i] = TileB::bload(rsb, (unsigned)(((long)relB[i] * g.ldv + kc) * 8), 0);
+        }
+    };
+    auto store_any = [&](auto bufc, int t) {
+        constexpr int buf = decltype(bufc)::value;
+        if (t < nfull) {
+            TileA::template sstore<false>(ra, swA + buf * TileA::LDS_ELEMS, 0, 0);
+            TileB::template sstore<false>(rb, swB + buf * TileB::LDS_ELEMS, 0, 0);
+        } else {
+            TileA::template sstore<true>(ra, swA + buf * TileA::LDS_ELEMS, ka0, K - t * BK);
+            TileB::template sstore<true>(rb, swB + buf * TileB::LDS_ELEMS, kb0, K - t * BK);
+        }
+    };
+    const int last_steps = (nk > nfull) ? (K - nfull * BK + 3) / 4 : BK / 4;
+    auto mma = [&](auto bufc, int steps) {
+        constexpr int buf = decltype(bufc)::value;
+        const double *sa = srA + buf * TileA::LDS_ELEMS;
+        const double *sb = srB + buf * TileB::LDS_ELEMS;
+#pragma unroll
+        for (int kk = 0; kk < BK / 4; ++kk) {
+            if (kk < steps) {                                  // wave-uniform
+                double a[2], b[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) a[i] = LDS_FRAG(sa + TileA::lds_index(i * 32, kk * 4));
+#pragma unroll
+                for (int j = 0; j < 2; ++j) b[j] = LDS_FRAG(sb + TileB::lds_index(j * 32, kk * 4));
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
+            }
+        }
+    };
+    load_any(0);
+    store_any(Buf0{}, 0);
+    __syncthreads();
+    int kt = 0;
+    for (; kt + 2 < nfull; kt += 2) {
+        load_full(kt + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        mma(Buf0{}, BK / 4);
+        __builtin_amdgcn_sched_barrier(0);
+        store_any(Buf1{}, kt + 1);
+        __syncthreads();
+        load_full(kt + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        mma(Buf1{}, BK / 4);
+        __builtin_amdgcn_sched_barrier(0);
+        store_any(Buf0{}, kt + 2);
+        __syncthreads();
+    }
+    if (kt + 1 < nk) {
+        load_any(kt + 1);
+        mma(Buf0{}, BK / 4);
+        store_any(Buf1{}, kt + 1);
+        __syncthreads();
+        if (kt + 2 < nk) {
+            load_any(kt + 2);
+            mma(Buf1{}, BK / 4);
+            store_any(Buf0{}, kt + 2);
+            __syncthreads();
+            mma(Buf0{}, last_steps);
+        } else {
+            mma(Buf1{}, last_steps);
+        }
+    } else {
+        mma(Buf0{}, last_steps);
+    }
+
+    // ---- epilogue: residual, optional mean in the (x, t, r) layout, the two sums over t of every column ----
+    const double half_log_2pi = 0.91893853320467274178;
+    const long rowlen = (long)g.nt * g.R;
+    double sl[2] = {0.0, 0.0}, se[2] = {0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const long rho = n0 + j * 32 + wc * 16 + fr;           // this lane's column (x, r)
+        if (rho < g.nrow) {
+            const long xx = rho / g.R;
+            const double *__restrict__ crow = g.c + xx * g.nt;
+            const double *__restrict__ yrow = g.y + rho * g.nt;
+            double *const mrow = g.mean ? g.mean + xx * rowlen + (rho - xx * g.R) : nullptr;
+#pragma unroll
+            for (int f = 0; f < 2; ++f)
+#pragma unroll
+                for (int r4 = 0; r4 < 4; ++r4) {
+                    const int tt = t0 + f * 32 + wr * 16 + fq + 4 * r4;
+                    if (tt >= g.nt) continue;
+                    const double b = acc[f][j][r4], cv = crow[tt];
+                    const double e = b / cv;
+                    if (mrow) mrow[(long)tt * g.R] = yrow[tt] - e;           // wave-uniform
+                    sl[j] += (0.5 * log(cv) - 0.5 * (b * e)) - half_log_2pi;
+                    se[j] += e * e;
+                }
+        }
+    }
+    // every lane takes part in the exchanges (a lane past an edge carries zeros)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        sl[j] += __shfl_xor(sl[j], 16, 64);
+        se[j] += __shfl_xor(se[j], 16, 64);
+        sl[j] += __shfl_xor(sl[j], 32, 64);
+        se[j] += __shfl_xor(se[j], 32, 64);
+        if (fq == 0) {
+            wsum[0][wr][j * 32 + wc * 16 + fr] = sl[j];
+            wsum[1][wr][j * 32 + wc * 16 + fr] = se[j];
+        }
+    }
+    __syncthreads();
+    if (tid < 2 * BN) {
+        const int q = tid >> 6, col = tid & 63;
+        const long rho = n0 + col;
+        if (rho < g.nrow) g.partials[((long)q * g.tiles_t + tile_t) * g.nrow + rho] = wsum[q][0][col] + wsum[q][1][col];
+    }
+}
+
+// lpd[rho] / sse[rho] = the partials of the time tiles, added in tile order
+__global__ __launch_bounds__(256) void loo_reduce_kernel(const double *__restrict__ p, int tiles, long nrow, double *lpd, double *sse) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < 2 * nrow; i += gridDim.x * 256L) {
+        const long q = i >= nrow ? 1 : 0, rho = i - q * nrow;
+        double s = 0.0;
+        for (int t = 0; t < tiles; ++t) s += p[(q * tiles + t) * nrow + rho];
+        (q ? sse : lpd)[rho] = s;
+    }
+}
+
+// var[i] = 1 / cdiag[i]: the leave-one-out predictive variance from the diagonal of K^-1
+__global__ __launch_bounds__(256) void loo_var_kernel(const double *__restrict__ cdiag, double *__restrict__ var, long n) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) var[i] = 1.0 / cdiag[i];
+}
+
+void k_loo_var(gpcsd_ctx *c, const double *cdiag, double *var, long n, hipStream_t s) {
+    ProfScope ps(c, "loo_var", 0.0, s);
+    hipLaunchKernelGGL(loo_var_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 1024)), dim3(256), 0, s, cdiag, var, n);
+    GP_HIP(hipGetLastError());
+}
+
+void gemm_loo(gpcsd_ctx *c, const LooDesc &d, hipStream_t s) {
+    GP_REQUIRE(d.nrow > 0 && d.nt > 0 && d.K > 0 && d.R > 0 && d.V && d.Qt && d.c && d.y && d.lpd && d.sse, -3, "gemm_loo: bad problem");
+    // 32-bit byte offsets inside one K tile of one block tile: 64 rows of V, 64 rows of Qt
+    GP_REQUIRE(d.ldv < (1L << 22) && d.ldq < (1L << 22) && d.nrow < (1L << 31), GPCSD_ERR_CAPACITY,
+               "gemm_loo: leading dimension %ld (or %ld rows) exceeds the capacity of one operand tile", std::max(d.ldv, d.ldq), d.nrow);
+    const int tiles_t = ceil_div(d.nt, 64);
+    const long tiles_c = (d.nrow + 63) / 64;
+    GP_REQUIRE(tiles_c * tiles_t < (1L << 31), GPCSD_ERR_CAPACITY, "gemm_loo: too many tiles");
+    LooK k;
+    k.V = d.V; k.ldv = d.ldv; k.Qt = d.Qt; k.ldq = d.ldq; k.c = d.c; k.y = d.y;
+    k.K = d.K; k.nt = d.nt; k.R = d.R; k.nrow = d.nrow;
+    k.mean = d.mean;
+    k.partials = c->buf<double>("loo_partials", (size_t)2 * tiles_t * d.nrow);
+    k.tiles_t = tiles_t;
+    {
+        ProfScope ps(c, "gemm_loo", 2.0 * (double)d.nrow * d.nt * (double)d.K, s);
+        hipLaunchKernelGGL(gemm_loo_kernel, dim3((unsigned)(tiles_c * tiles_t)), dim3(256), 0, s, k);
+        GP_HIP(hipGetLastError());
+    }
+    {
+        ProfScope ps(c, "loo_reduce", 0.0, s);
+        const unsigned nb = (unsigned)std::min<long>((2 * d.nrow + 255) / 256, 1024);
+        hipLaunchKernelGGL(loo_reduce_kernel, dim3(nb), dim3(256), 0, s, (const double *)k.partials, tiles_t, d.nrow, d.lpd, d.sse);
+        GP_HIP(hipGetLastError());
+    }
+}
+
 // Deterministic final reduction of per-block partials (single workgroup, fixed tree).
 // A second workgroup may carry an unrelated reduction of the same shape (p2, n2 -> out2: the sum of log D partials of the
 // likelihood, which would otherwise be a launch of its own in the dependent tail of the call).

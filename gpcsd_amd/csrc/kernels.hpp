@@ -123,6 +123,29 @@ struct VarDesc {
 };
 void gemm_var(gpcsd_ctx *c, const VarDesc &d, hipStream_t s);
 
+// Last product of the leave-one-out scores (gpcsd_loo; gemm_f64.hip: gemm_loo_kernel) with everything that follows it in its
+// epilogue: beta[(x, r)][t] = sum_i V[(x, r)][i] Qt[t][i] = (K^-1 y_r)[x, t] is never stored.  Per element, with c[x][t] the
+// diagonal of K^-1 and y[(x, r)][t] the data in the resident row layout,
+//   e = beta / c                          (the leave-one-out residual y - loo_mean)
+//   mean[x][t][r] = y - e                 (optional; the reference's (nx, nt, ntrials) layout)
+//   lpd[(x, r)] = sum_t 1/2 log c - 1/2 beta e - 1/2 log 2 pi,      sse[(x, r)] = sum_t e^2
+// The two row sums are deterministic: registers, the four lane groups of a wave, the two waves of a tile's time half through LDS,
+// then one partial per time tile and row in `partials` ([2][tiles_t][nrow]), added in tile order by a second small launch.
+struct LooDesc {
+    const double *V = nullptr;      // [(x, r)][K] row-major
+    long ldv = 0;
+    const double *Qt = nullptr;     // [nt][K] row-major
+    long ldq = 0;
+    const double *c = nullptr;      // [nx][nt]
+    const double *y = nullptr;      // [(x, r)][nt]
+    int K = 0, nt = 0, R = 0;
+    long nrow = 0;                  // nx * R
+    double *mean = nullptr;         // (nx, nt, R) or nullptr
+    double *lpd = nullptr, *sse = nullptr;      // [nrow] each
+};
+void gemm_loo(gpcsd_ctx *c, const LooDesc &d, hipStream_t s);
+void k_loo_var(gpcsd_ctx *c, const double *cdiag, double *var, long n, hipStream_t s);      // var = 1 / cdiag elementwise
+
 // ---------------------------------------------------------------- batched hyper-parameter sets
 // Device image of gpcsd_hparams for batched evaluations (gpcsd_loglik_grad_batch): one entry per hyper-parameter set.  The
 // Gram builders / derivative kernels take an optional table: with `tab` they run once for all B sets (the set index is a grid

@@ -819,6 +819,47 @@ class GPCSDModel:
         self.t_var = tstar
         self.x_var = z
 
+    def loo(self, mean=True, resident=False):
+        """Leave-one-out cross-validation of the model under its current hyper-parameters, in closed form and without a refit
+        (Rasmussen & Williams, Gaussian Processes for Machine Learning, 5.4.2): how well the fitted model explains the recording
+        it was fitted to -- to choose between restarts, noise models or numbers of temporal components, and to find the electrode
+        or trial the model does not describe.  Returns the total log predictive density, the sum of `loo_lpd`, as a float.
+
+        K is the covariance of the data exactly as `loglik()` sees it: (Ks + JITTER I) (x) Kt + noise, through its eigen-form
+        (Qs (x) Qt) diag(D) (Qs (x) Qt)^T with D[x', i'] = es[x'] et[i'] + sig2n; the jitter sits on Ks, and a per-electrode noise
+        list sits on the eigen-index x' as in the reference's comp_eig_D (utility_functions.py:54-63).  User-defined temporal
+        covariances are allowed (only Kt on the training grid is used).  With c = diag(K^-1) and beta_r = K^-1 y_r it sets
+
+          loo_var   (nx, nt)           1 / c: the predictive variance of the NOISY sample given all other samples of its trial
+          loo_mean  (nx, nt, ntrials)  y - beta / c, or None with mean=False (which also spares the device its stores)
+          loo_lpd   (nx, ntrials)      sum over t of 1/2 log c - 1/2 beta^2 / c - 1/2 log(2 pi)
+          loo_sse   (nx, ntrials)      sum over t of the squared leave-one-out residual (y - loo_mean)^2
+
+        Per-electrode and per-trial scores are `loo_lpd.sum(1)` and `loo_lpd.sum(0)`.  Unlike `loglik()` the log density KEEPS its
+        2 pi constant: it is a density per sample, meant to be compared across models and data sizes.  The sums are formed in a
+        fixed order: the same call gives the same bits.  resident=True: zero-copy device views as in `predict`.  `csd_pred`,
+        `lfp_pred`, the `*_var` attributes and `t_pred` are left alone.  Under trial sharding the per-trial arrays are this rank's
+        block of trials, `loo_var` is the same on every rank and the returned total is summed over the ranks.  No reference
+        counterpart."""
+        ctx = self._sync_device()
+        hp, _keep = self._hparams(self.JITTER)             # the jitter of loglik
+        nx, nt, R_local = self._local_lfp().shape
+        if resident:
+            ctx.loo_resident(hp, want_mean=mean)
+            self.loo_var = ctx.device_array("loo_var", (nx, nt))
+            self.loo_lpd = ctx.device_array("loo_lpd", (nx, R_local))
+            self.loo_sse = ctx.device_array("loo_sse", (nx, R_local))
+            self.loo_mean = ctx.device_array("loo_mean", (nx, nt, R_local)) if mean else None
+            total = float(np.sum(ctx.fetch("loo_lpd", (nx, R_local))))
+        else:
+            res = ctx.loo(hp, (nx, nt, R_local), want_mean=mean)
+            self.loo_var, self.loo_lpd, self.loo_sse, self.loo_mean = res["var"], res["lpd"], res["sse"], res["mean"]
+            total = float(np.sum(res["lpd"]))
+        sh = getattr(self, "_sharding", None)
+        if sh is not None:
+            total = float(sh.allreduce_sum(np.array([total]))[0])
+        return total
+
     def loglik_predict_many(self, param_sets, z, t, type="csd", resident=False, share_spatial=False):
         """loglik() and predict(z, t, type) under each of a LIST of hyper-parameter sets -- dicts as extract_model_params() returns
         them: the optima of every restart of a fit, a grid, posterior draws -- in order.  Returns the log-likelihoods, one per set;

@@ -350,6 +350,32 @@ int gpcsd_predict_var_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const do
  * P is squared on its way to the multiplier; prior_s kd - sum is one fused multiply-add. */
 int gpcsd_var_contract(gpcsd_ctx *ctx, const double *G, int nz, int K, const double *P, int C, int nts,
                        const double *prior_s, const double *kd, double *out);
+/* Leave-one-out cross-validation of the fitted Gaussian process, in closed form and without a refit (Rasmussen & Williams, Gaussian
+ * Processes for Machine Learning, 5.4.2).  NO REFERENCE COUNTERPART: the reference would need the diagonal of the inverse of the
+ * (nx nt)^2 covariance.  K is the covariance of the data exactly as gpcsd_loglik sees it: K = (Qs (x) Qt) diag(D) (Qs (x) Qt)^T
+ * with Ks + hp->jitter I = Qs diag(es) Qs^T, Kt = Qt diag(et) Qt^T, D[x', i'] = es[x'] et[i'] + sig2n -- a per-electrode noise list
+ * on the eigen-index x' as utility_functions.py:54-63; a user-defined temporal Gram (GPCSD_KIND_HOST) is allowed.  For sample (x, t)
+ * of trial r, with c = diag(K^-1) (trial-independent) and beta_r = K^-1 y_r:
+ *   loo_var[x, t]     = 1 / c[x, t]                      predictive variance of the NOISY sample given all others
+ *   loo_mean[x, t, r] = y_r[x, t] - beta_r[x, t] / c[x, t]
+ *   lpd_r[x, t]       = 1/2 log c - 1/2 beta_r^2 / c - 1/2 log(2 pi)      (a density per sample: unlike gpcsd_loglik it KEEPS the
+ *                                                                           2 pi constant, to be compared across models and sizes)
+ * Outputs (any may be NULL; mean == NULL also skips its stores on the device): var (nx, nt); mean (nx, nt, ntrials), the layout of
+ * the data; lpd and sse (nx, ntrials) = the sums over t of lpd_r and of the squared residual (beta_r / c)^2.  The sums are formed in
+ * a fixed order without atomics: the same call returns the same bits.  Capacity (ntrials * nt >= GPCSD_MAX_GEMM_LD_KMAJOR or
+ * nx * ntrials >= 2^31) returns GPCSD_ERR_CAPACITY before anything is read; rc -4 without resident data. */
+int gpcsd_loo(gpcsd_ctx *ctx, const gpcsd_hparams *hp, double *var, double *mean, double *lpd, double *sse);
+/* Same computation (no reference counterpart), results left in the named device buffers "loo_var" (nx*nt), "loo_lpd" and "loo_sse"
+ * (nx*ntrials each) and, when want_mean != 0, "loo_mean" (nx*nt*ntrials) for gpcsd_fetch / gpcsd_device_buffer.  Waits for its own
+ * work: a numerical failure (rc > 0) is returned by the call itself.  The buffers of the predictions are left alone. */
+int gpcsd_loo_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, int want_mean);
+/* The last product of gpcsd_loo alone, on host arrays (no reference counterpart; upload, the launch and its reduce, download):
+ * V (nx * R, K) and Qt (nt, K) give beta[(x, r)][t] = sum_k V[(x, r)][k] Qt[t][k], which is never stored; with c (nx, nt) > 0 and
+ * Y (nx * R, nt): e = beta / c, mean[x][t][r] = Y[(x, r)][t] - e (mean may be NULL), lpd[(x, r)] = sum_t 1/2 log c - 1/2 beta e -
+ * 1/2 log(2 pi), sse[(x, r)] = sum_t e^2.  K is the contracted length (nt in gpcsd_loo).  Capacity as gpcsd_loo, checked before
+ * anything is read. */
+int gpcsd_loo_contract(gpcsd_ctx *ctx, const double *V, const double *Qt, const double *c, const double *Y, int nx, int R, int nt,
+                       int K, double *mean, double *lpd, double *sse);
 /* copy `count` doubles of the named ctx-owned device buffer to host; rc -2 if the name is unknown; rc > 0 if the
  * asynchronous gpcsd_predict_resident that produced the buffer failed numerically */
 int gpcsd_fetch(gpcsd_ctx *ctx, const char *name, double *host, long count);
