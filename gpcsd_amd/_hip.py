@@ -174,6 +174,10 @@ SIGNATURES = {
     "gpcsd_fetch": (_I, [_P, ctypes.c_char_p, _DP, _L]),
     "gpcsd_device_buffer": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
     "gpcsd_sample_prior": (_I, [_P, ctypes.POINTER(HParams), _I, _DP, _I, _DP]),
+    "gpcsd_normals": (_I, [_P, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_ulonglong, _L, _DP]),
+    "gpcsd_set_trial_offset": (_I, [_P, _L]),
+    "gpcsd_sample_posterior": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _I, ctypes.c_ulonglong, _DP, _DP, _DP, _DP]),
+    "gpcsd_sample_posterior_resident": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _I, ctypes.c_ulonglong, _DP, _DP]),
     "gpcsd_set_gram_precision": (_I, [_P, _I]),
     "gpcsd_fold_gemm": (_I, [_P, _I, ctypes.POINTER(_L)]),
     "gpcsd_ll_tridiag": (_I, [_P, _I, ctypes.POINTER(_L)]),
@@ -208,6 +212,7 @@ SIGNATURES = {
     "gpcsd_prof_names": (_I, [_P, ctypes.c_char_p, _I]),
     "gpcsd_mfma_f64_peak": (_I, [_P, _DP]),
     "gpcsd_hbm_copy_peak": (_I, [_P, _L, _DP]),
+    "gpcsd_normals_bench": (_I, [_P, _L, _I, _DP]),
     "gpcsd_gemm_bench": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _DP]),
     "gpcsd_potrf_bench": (_I, [_P, _I, _I, _DP]),
     "gpcsd_potrf_gate_timeouts": (_I, [_P, ctypes.POINTER(_L)]),
@@ -981,6 +986,34 @@ class Context:
         self._check(self._lib.gpcsd_sample_prior(self._h, ctypes.byref(hp), int(which), _ptr(normals), normals.shape[2], _ptr(out)))
         return out
 
+    def normals(self, seed, stream, first, count):
+        """Standard normals first .. first + count - 1 of stream `stream` under `seed` from the device generator (gpcsd_normals)."""
+        out = np.empty(int(count))
+        self._check(self._lib.gpcsd_normals(self._h, int(seed), int(stream), int(first), int(count), _ptr(out)))
+        return out
+
+    def set_trial_offset(self, first):
+        """Global index of the first resident trial (a rank's block of a trial-sharded job); sample_posterior indexes its normals by it."""
+        self._check(self._lib.gpcsd_set_trial_offset(self._h, int(first)))
+
+    def sample_posterior(self, hp, z, tstar, type_code, nsamples, seed, R, xi=None, eps=None, resident=False):
+        """Joint posterior draws (gpcsd_sample_posterior): dict with "csd" / "lfp" (nz, ntstar, R, nsamples) for the requested type
+        -- host arrays, or with resident=True nothing (the draws stay in "post_sample_csd" / "post_sample_lfp").  xi, eps: host
+        normals (R, nsamples, ns, ntt) / (R, nsamples, nx, nt), or both None for the device generator."""
+        z = _arr(z)
+        tstar = _arr(tstar).reshape(-1)
+        xi = None if xi is None else _arr(xi)
+        eps = None if eps is None else _arr(eps)
+        args = (self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size, int(type_code), int(nsamples), int(seed),
+                _ptr(xi), _ptr(eps))
+        if resident:
+            self._check(self._lib.gpcsd_sample_posterior_resident(*args))
+            return {}
+        bufs = {name: pinned_pool.empty((z.shape[0], tstar.size, int(R), int(nsamples))) if type_code & bit else None
+                for name, bit in (("csd", PRED_CSD), ("lfp", PRED_LFP))}
+        self._check(self._lib.gpcsd_sample_posterior(*args, _ptr(bufs["csd"]), _ptr(bufs["lfp"])))
+        return {k: v for k, v in bufs.items() if v is not None}
+
     # ---- measurement ----
     def synchronize(self):
         self._check(self._lib.gpcsd_device_synchronize(self._h))
@@ -1129,6 +1162,12 @@ class Context:
     def hbm_copy_peak(self, nbytes=1 << 30):
         out = ctypes.c_double()
         self._check(self._lib.gpcsd_hbm_copy_peak(self._h, int(nbytes), ctypes.byref(out)))
+        return out.value
+
+    def normals_bench(self, count=1 << 27, reps=10):
+        """GB/s of normals written by the device generator alone (gpcsd_normals_bench)."""
+        out = ctypes.c_double()
+        self._check(self._lib.gpcsd_normals_bench(self._h, int(count), int(reps), ctypes.byref(out)))
         return out.value
 
 

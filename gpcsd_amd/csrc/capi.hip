@@ -1322,6 +1322,7 @@ extern "C" int gpcsd_set_lfp(gpcsd_ctx *c, const double *lfp, int nx, int nt, in
     k_swap_last2(c, stage, c->d_lfp, nx, nt, ntrials, c->stream);     // (x,t,r) -> (x,r,t)
     c->sync();
     c->nx = nx; c->nt = nt; c->ntrials = ntrials;
+    c->trial_offset = 0;                   // new data: trial 0 again until gpcsd_set_trial_offset says which block it is
     c->lfp_fold_sig = 0;
     return 0;
     GP_API_END(c)
@@ -1409,6 +1410,7 @@ extern "C" int gpcsd_set_time(gpcsd_ctx *c, const double *t, int nt) {
 
 #include "capi_operators.inl"
 #include "capi_fused.inl"
+#include "capi_sample.inl"
 #include "capi_grad.inl"
 #include "capi_measure.inl"
 #include "capi_dist.inl"

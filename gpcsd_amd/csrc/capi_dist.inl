@@ -113,7 +113,8 @@ extern "C" int gpcsd_dist_set_lfp(gpcsd_dist *d, const double *lfp, int nx, int 
         const int f = first[i], cnt = count[i];
         std::vector<double> blk((size_t)nx * nt * cnt);
         for (long r = 0; r < (long)nx * nt; ++r) memcpy(&blk[(size_t)r * cnt], lfp + (size_t)r * ntrials + f, (size_t)cnt * sizeof(double));
-        return gpcsd_set_lfp(d->ctx[i], blk.data(), nx, nt, cnt);
+        const int rc_i = gpcsd_set_lfp(d->ctx[i], blk.data(), nx, nt, cnt);
+        return rc_i != 0 ? rc_i : gpcsd_set_trial_offset(d->ctx[i], f);      // the block's place among all trials (posterior draws)
     });
     if (rc != 0) {                       // some contexts may hold the new data, some the old: the handle holds none
         d->nx = d->nt = d->ntrials = 0;

@@ -754,18 +754,19 @@ static void pred_cross_front(gpcsd_ctx *c, const gpcsd_hparams *hp, EigState &e,
 }
 // The part of it that reads the trials and neither sites nor times (all the leave-one-out scores need), in two steps because the
 // second one needs the joined temporal side: W = Qs^T Y (spatial side only), then Bm = (W Qt) / D.
-static void pred_data_spatial(gpcsd_ctx *c, EigState &e, double *W) {
+// Y: R trials -- the resident data, or the residuals of a chunk of posterior draws -- as [x][r][t].
+static void pred_data_spatial(gpcsd_ctx *c, EigState &e, double *W, const double *Y, int R) {
     const int nx = c->nx;
-    const long RT = (long)c->ntrials * c->nt;
+    const long RT = (long)R * c->nt;
     GemmDesc g1;                          // W = Qs^T Y
     g1.M = nx; g1.N = (int)RT; g1.K = nx;
     g1.A = e.Qs; g1.lda = nx; g1.transA = true;
-    g1.B = c->d_lfp; g1.ldb = RT; g1.C = W; g1.ldc = RT;
+    g1.B = Y; g1.ldb = RT; g1.C = W; g1.ldc = RT;
     g1.prof_name = "gemm_proj_spatial";
     gemm_f64(c, g1, c->stream);
 }
-static void pred_data_temporal(gpcsd_ctx *c, EigState &e, const double *W, double *Bm) {
-    const int nx = c->nx, nt = c->nt, R = c->ntrials;
+static void pred_data_temporal(gpcsd_ctx *c, EigState &e, const double *W, double *Bm, int R) {
+    const int nx = c->nx, nt = c->nt;
     GemmDesc g2;                          // Bm = (W Qt) / D
     g2.M = nx * R; g2.N = nt; g2.K = nt;
     g2.A = W; g2.lda = nt; g2.B = e.Qt; g2.ldb = nt; g2.C = Bm; g2.ldc = nt;
@@ -779,9 +780,9 @@ static PredFullFront predict_full_front(gpcsd_ctx *c, const gpcsd_hparams *hp, E
     double *W = c->buf<double>("proj_W", (size_t)c->nx * RT);
     PredFullFront f;
     f.Bm = c->buf<double>("pred_B", (size_t)c->nx * RT);
-    pred_data_spatial(c, e, W);
+    pred_data_spatial(c, e, W, c->d_lfp, c->ntrials);
     pred_cross_front(c, hp, e, z, nz, tstar, ntstar, type, f);
-    pred_data_temporal(c, e, W, f.Bm);
+    pred_data_temporal(c, e, W, f.Bm, c->ntrials);
     return f;
 }
 
@@ -1205,6 +1206,23 @@ extern "C" int gpcsd_predict(gpcsd_ctx *c, const gpcsd_hparams *hp, const double
     GP_API_END(c)
 }
 
+// The temporal operand of the predictions at arbitrary times (gpcsd_predict_at, gpcsd_predict_var, gpcsd_sample_posterior), on the
+// main stream behind the joined temporal side: Pcat[i'][cc * ntstar + j] = sum_i Qt[i][i'] k_cc(t*_j, t_i), the TRAINING axis of the
+// cross Grams Kts (C, ntstar, nt) contracted, the components side by side in "pred_Pc" (nt, C * ntstar).
+static double *pred_at_Pc(gpcsd_ctx *c, const EigState &e, const double *Kts, int C, int ntstar) {
+    const int nt = c->nt;
+    double *Pc = c->buf<double>("pred_Pc", (size_t)C * nt * ntstar);
+    for (int cc = 0; cc < C; ++cc) {
+        GemmDesc gp;
+        gp.M = nt; gp.N = ntstar; gp.K = nt;
+        gp.A = e.Qt; gp.lda = nt; gp.transA = true; gp.B = Kts + (size_t)cc * ntstar * nt; gp.ldb = nt; gp.transB = true;
+        gp.C = Pc + (size_t)cc * ntstar; gp.ldc = (long)C * ntstar;
+        gp.prof_name = "gemm_pred_Pc";
+        gemm_f64(c, gp, c->stream);
+    }
+    return Pc;
+}
+
 // Posterior mean at ARBITRARY prediction times (gpcsd_predict_at; no reference counterpart): as the full-size path of predict_impl
 // up to S = (Kc^T Qs) Bm, then the TRAINING axis of the cross Grams is contracted,
 //   P_c[i'][j] = sum_i Qt[i][i'] k_c(t*_j, t_i),      out_c[z][j][r] = sum_i' S[(z, r)][i'] P_c[i'][j],
@@ -1231,16 +1249,8 @@ static int predict_at_impl(gpcsd_ctx *c, const PredCall &q) {
     const PredFullFront f = predict_full_front(c, hp, e, z, nz, tstar, ntstar, type);
     double *const Bm = f.Bm, *const M1 = f.M1, *const Kts = f.Kts;
     double *S = c->buf<double>("pred_S", (size_t)nz * RT);
-    double *Pc = c->buf<double>("pred_Pc", (size_t)C * nt * ntstar);
+    double *Pc = pred_at_Pc(c, e, Kts, C, ntstar);
     const size_t out_elems = (size_t)nz * ntstar * R;
-    for (int cc = 0; cc < C; ++cc) {
-        GemmDesc gp;                      // Pcat[i'][cc*ntstar + j] = sum_i Qt[i][i'] Ktstar_cc[j][i]: the TRAINING axis contracted
-        gp.M = nt; gp.N = ntstar; gp.K = nt;
-        gp.A = e.Qt; gp.lda = nt; gp.transA = true; gp.B = Kts + (size_t)cc * ntstar * nt; gp.ldb = nt; gp.transB = true;
-        gp.C = Pc + (size_t)cc * ntstar; gp.ldc = (long)C * ntstar;
-        gp.prof_name = "gemm_pred_Pc";
-        gemm_f64(c, gp, s);
-    }
     for (int which = 1; which <= 2; ++which) {
         if (!(type & which)) continue;
         const PredOut out = pred_out_bufs(c, which, out_elems, C, want_lists);
@@ -1308,18 +1318,10 @@ static int predict_var_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const double 
     hipStream_t s = c->stream;
     PredFullFront f{nullptr, nullptr, nullptr};
     pred_cross_front(c, hp, e, z, nz, tstar, ntstar, type, f);
-    double *Pc = c->buf<double>("pred_Pc", (size_t)C * nt * ntstar);
+    double *Pc = pred_at_Pc(c, e, f.Kts, C, ntstar);
     double *G = c->buf<double>("pred_var_G", (size_t)nz * nt);
     double *prior = c->buf<double>("pred_var_prior", (size_t)nz);
     const double *dz = (const double *)c->bufs["pred_z"].p;
-    for (int cc = 0; cc < C; ++cc) {
-        GemmDesc gp;                      // Pcat[i'][cc*ntstar + j] = sum_i Qt[i][i'] Ktstar_cc[j][i]: the TRAINING axis contracted
-        gp.M = nt; gp.N = ntstar; gp.K = nt;
-        gp.A = e.Qt; gp.lda = nt; gp.transA = true; gp.B = f.Kts + (size_t)cc * ntstar * nt; gp.ldb = nt; gp.transB = true;
-        gp.C = Pc + (size_t)cc * ntstar; gp.ldc = (long)C * ntstar;
-        gp.prof_name = "gemm_pred_Pc";
-        gemm_f64(c, gp, s);
-    }
     const size_t out_elems = (size_t)nz * ntstar;
     for (int which = 1; which <= 2; ++which) {
         if (!(type & which)) continue;
@@ -1400,7 +1402,7 @@ static int loo_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, bool want_mean) {
     double *var = c->buf<double>("loo_var", (size_t)nx * nt);
     double *lpd = c->buf<double>("loo_lpd", (size_t)nrow), *sse = c->buf<double>("loo_sse", (size_t)nrow);
     double *mean = want_mean ? c->buf<double>("loo_mean", (size_t)nx * RT) : nullptr;
-    pred_data_spatial(c, e, W);
+    pred_data_spatial(c, e, W, c->d_lfp, R);
     join_temporal(c, e, nullptr, false);           // nobody reads sum(log D) here
     VarDesc v1;                           // H[x][i'] = sum_x' Qs[x][x']^2 Dinv[x'][i']
     v1.A = e.Qs; v1.lda = nx; v1.B = e.Dinv; v1.ldb = nt;
@@ -1414,7 +1416,7 @@ static int loo_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, bool want_mean) {
     v2.prof_name = "gemm_var_c";
     gemm_var(c, v2, s);
     k_loo_var(c, cdiag, var, (long)nx * nt, s);
-    pred_data_temporal(c, e, W, Bm);
+    pred_data_temporal(c, e, W, Bm, R);
     GemmDesc g3;                          // V[x][(r,i')] = sum_x' Qs[x][x'] Bm[x'][(r,i')]
     g3.M = nx; g3.N = (int)RT; g3.K = nx;
     g3.A = e.Qs; g3.lda = nx; g3.B = Bm; g3.ldb = RT; g3.C = V; g3.ldc = RT;

@@ -150,6 +150,28 @@ extern "C" int gpcsd_hbm_copy_peak(gpcsd_ctx *c, long bytes, double *gbs) {
 }
 
 
+// The device generator alone (rng.hip): `count` normals of stream 0 written to a device buffer, nothing copied out; one untimed
+// launch, then `reps` launches between two events.  *gbs = bytes of normals written per second (8 count reps / time), the figure to
+// set against gpcsd_hbm_copy_peak's (which counts its reads as well as its writes).
+extern "C" int gpcsd_normals_bench(gpcsd_ctx *c, long count, int reps, double *gbs) {
+    GP_API_BEGIN(c)
+    GP_REQUIRE(gbs != nullptr && count >= (1 << 17) && reps > 0, -3, "normals_bench: need >= 2^17 normals and reps > 0");
+    double *d = c->buf<double>("rng_out", (size_t)count);
+    hipEvent_t e0 = c->get_event(), e1 = c->get_event();
+    k_normals(c, 1ull, 0u, 0ull, count, d, c->stream);
+    GP_HIP(hipEventRecord(e0, c->stream));
+    for (int i = 0; i < reps; ++i) k_normals(c, 1ull, 0u, (unsigned long long)i * (unsigned long long)count, count, d, c->stream);
+    GP_HIP(hipEventRecord(e1, c->stream));
+    GP_HIP(hipEventSynchronize(e1));
+    float ms = 0.f;
+    GP_HIP(hipEventElapsedTime(&ms, e0, e1));
+    *gbs = 8.0 * (double)count * reps / (ms * 1e-3) / 1e9;
+    c->event_pool.push_back(e0);
+    c->event_pool.push_back(e1);
+    return 0;
+    GP_API_END(c)
+}
+
 // Device-resident timing of the blocked Cholesky (chol.hip) at order n: a well-conditioned SPD test matrix is generated on the
 // device before every repetition (A_ij = exp(-|i - j| / 64) + [i == j]: an exponential-kernel Gram matrix plus a unit nugget),
 // HIP events on the call's stream bracket potrf_device alone.  ms_out: mean over reps (after one untimed repetition).  With

@@ -214,6 +214,8 @@ struct gpcsd_ctx {
     int geo_nx = 0, ngl1 = 0, ngl2 = 0;     // geometry
     int time_nt = 0;
     double *d_lfp = nullptr;                // [x][r][t]
+    long trial_offset = 0;                  // global index of the first resident trial (gpcsd_set_trial_offset): a rank's block of a
+                                            // trial-sharded job draws the normals the unsharded job would (gpcsd_sample_posterior)
     gpcsd::SymDev sym_s, sym_t;             // reflection symmetry of the electrode / time grids (ns == 0: none found)
     // folded-basis GEMMs (capi.hip): what the electrode symmetry reflects about, host copies of the grids to recognise
     // prediction sites / times with the same symmetry, the symmetry of the last prediction sites, and whether the

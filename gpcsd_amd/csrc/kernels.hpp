@@ -240,6 +240,24 @@ void k_fold_lfp(gpcsd_ctx *c, const double *Y, int nx, int R, int nt, const SymD
 void k_unfold_swap_sum(gpcsd_ctx *c, const double *in, int C, double *list, long list_stride, double *sum, int R, int nt,
                        const SymDev &sz, const SymDev &st, hipStream_t s, int nsP = 0, int naP = 0, long ldin = 0);
 
+// ---------------------------------------------------------------- device normals and the passes of a posterior draw (rng.hip)
+// out[k] = standard normal number first + k of stream `stream` under `seed`, k < count: Philox4x32-10 + Box-Muller in fp64
+// (philox.hpp), a function of (seed, stream, index) alone
+void k_normals(gpcsd_ctx *c, unsigned long long seed, unsigned stream, unsigned long long first, long count, double *out, hipStream_t s);
+// out[x][q][t] = y[x][(p0 + q) / S][t] - phi[x][q][t] - eps[x][q][t], q < np: the residual of the pseudo-trials p0 .. p0 + np - 1
+// (p = r S + s) in the layout the projection reads; y holds R trials as [x][r][t]; out may be phi
+void k_sample_residual(gpcsd_ctx *c, const double *y, const double *phi, const double *eps, double *out, int nx, int nt, int R, long p0,
+                       int np, int S, hipStream_t s);
+// block (r0.., c0..) of the symmetric J (n, n) and its mirror image from src (nr, nc); a diagonal block from src's lower triangle
+void k_sym_place(gpcsd_ctx *c, double *J, int n, int r0, int c0, const double *src, int nr, int nc, hipStream_t s);
+// dsq = sqrt(diag J), dinv = 1 / dsq, J <- diag(dinv) J diag(dinv) (unit diagonal; symmetric in, symmetric out)
+void k_sym_equilibrate(gpcsd_ctx *c, double *J, int n, double *dsq, double *dinv, hipStream_t s);
+// F[i][k] = rowscale[i] Q[i][k] sqrt(max(w[k], 0)); rowscale may be null, nw == 1 broadcasts w[0]; F may be Q
+void k_eig_factor(gpcsd_ctx *c, const double *Q, const double *w, int nw, const double *rowscale, double *F, int n, hipStream_t s);
+// out[z][j][p0 + q] = upd[z][j][q] + prior[z][q][j], q < np, out rows of P pseudo-trials
+void k_sample_combine(gpcsd_ctx *c, const double *upd, const double *prior, double *out, int nz, int nts, int np, long P, long p0,
+                      hipStream_t s);
+
 // ---------------------------------------------------------------- eigensolver (eigh.hip)
 // Symmetric eigendecomposition of A (n,n) on device.  evals ascending; evecs (n,n) row-major with
 // eigenvectors in COLUMNS (numpy.linalg.eigh convention).  A is destroyed.  status: device int (0 ok).

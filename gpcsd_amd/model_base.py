@@ -915,6 +915,72 @@ class GPCSDModel:
         self._store_predictions(res, z, t)
         return out
 
+    _SAMPLE_BUFFERS = (("csd", _hip.PRED_CSD, "post_sample_csd"), ("lfp", _hip.PRED_LFP, "post_sample_lfp"))
+
+    def _sample_posterior_args(self, z, tstar, type, nsamples):
+        """Validation and shapes shared by sample_posterior and _sample_posterior_from_normals; opens no context."""
+        if type not in ("csd", "lfp", "both"):
+            raise ValueError("type must be 'csd', 'lfp' or 'both'")
+        z = np.asarray(z, dtype=np.float64)
+        z2 = z.reshape(-1, 1) if self.dim == 1 else z
+        tstar = np.asarray(tstar)
+        if tstar.size < 1:
+            raise ValueError("tstar must hold at least one time")
+        if int(nsamples) < 1:
+            raise ValueError("nsamples must be at least 1")
+        if self._uses_host_kt():
+            raise NotImplementedError("sample_posterior: a user-defined temporal covariance has no joint Gram over [t*; t] on the device; "
+                                      "only GPCSDTemporalCovSE / GPCSDTemporalCovMatern components are supported")
+        sh = getattr(self, "_sharding", None)
+        if sh is not None and getattr(sh, "gather_predictions", False):
+            raise NotImplementedError("sample_posterior: gather_predictions does not apply to draws; each rank returns its block of trials")
+        code = {"csd": _hip.PRED_CSD, "lfp": _hip.PRED_LFP, "both": _hip.PRED_BOTH}[type]
+        return z2, tstar, code, sh
+
+    def _sample_posterior_call(self, z2, tstar, code, sh, nsamples, seed, xi, eps, resident):
+        ctx = self._sync_device()
+        hp, _keep = self._hparams(0.0)                     # no jitter, as predict
+        R_local = self._local_lfp().shape[2]
+        # a rank's block of trials draws the normals the unsharded job draws for those trials
+        ctx.set_trial_offset(0 if sh is None else sh.local_slice(np.atleast_3d(self.lfp).shape[2]).start or 0)
+        res = ctx.sample_posterior(hp, z2, tstar, code, nsamples, seed, R_local, xi=xi, eps=eps, resident=resident)
+        if resident:
+            shape = (z2.shape[0], tstar.size, R_local, int(nsamples))
+            res = {name: ctx.device_array(buf, shape) for name, bit, buf in self._SAMPLE_BUFFERS if code & bit}
+        return res.get("csd"), res.get("lfp")
+
+    def sample_posterior(self, z, tstar, nsamples=1, type="csd", seed=1, resident=False):
+        """Joint draws from the posterior of the CSD and/or LFP at sites z and ARBITRARY times tstar: `nsamples` fields per (local)
+        trial, each consistent with that trial's recording.  Returns (csd, lfp), arrays of shape (nz, ntstar, ntrials, nsamples)
+        with None for the part not requested; resident=True returns zero-copy device views as in `predict`.  What `csd_var` cannot
+        give -- the uncertainty of a peak latency, a sink's extent, a phase: any nonlinear functional of a whole (z, t) field --
+        comes from pushing these draws through the same pipeline as the posterior mean.
+
+        The model is the one whose mean `predict_at` and whose variance `predict_var` return: no jitter, a per-electrode noise
+        list on the eigen-index as in loglik, and the LFP is the noise-free potential.  Draws are of the SUM of the temporal
+        components (a joint draw does not identify them separately).  Each draw is f_prior + P (y - phi - eps) (Matheron's rule)
+        with a joint prior draw (f_prior, phi), a noise draw eps and the linear map P of `predict_at`; the normals come from a
+        counter-based generator on the GPU, so the same `seed` gives the same draws, however the work is chunked and -- under
+        trial sharding, where each rank returns its block of trials -- however the trials are spread over ranks.
+        `gather_predictions` does not apply (NotImplementedError), nor do user-defined temporal covariances.  The prediction,
+        variance and leave-one-out attributes are left alone.  No reference counterpart (the reference has sample_prior only)."""
+        z2, tstar, code, sh = self._sample_posterior_args(z, tstar, type, nsamples)
+        return self._sample_posterior_call(z2, tstar, code, sh, int(nsamples), int(seed), None, None, resident)
+
+    def _sample_posterior_from_normals(self, z, tstar, type, xi, eps):
+        """The affine map normals -> draws for host-supplied standard normals: xi (ntrials, nsamples, ns, ntt) with rows
+        [CSD(z) if asked; LFP(z) if asked; LFP(x)] and columns [t*; t], eps (ntrials, nsamples, nx, nt).  For tests."""
+        xi, eps = np.asarray(xi, dtype=np.float64), np.asarray(eps, dtype=np.float64)
+        if xi.ndim != 4 or eps.ndim != 4 or xi.shape[:2] != eps.shape[:2]:
+            raise ValueError("xi (ntrials, nsamples, ns, ntt) and eps (ntrials, nsamples, nx, nt) must share their first two axes")
+        z2, tstar, code, sh = self._sample_posterior_args(z, tstar, type, xi.shape[1])
+        nx, nt, R_local = self._local_lfp().shape
+        ns = z2.shape[0] * (2 if type == "both" else 1) + nx
+        if xi.shape != (R_local, xi.shape[1], ns, tstar.size + nt) or eps.shape[2:] != (nx, nt):
+            raise ValueError("xi must be (%d, nsamples, %d, %d) and eps (%d, nsamples, %d, %d)"
+                             % (R_local, ns, tstar.size + nt, R_local, nx, nt))
+        return self._sample_posterior_call(z2, tstar, code, sh, xi.shape[1], 0, xi, eps, False)
+
     def _sample_prior_from_normals(self, normals, which):
         """Ls Z_r Lt^T on the GPU for host-supplied standard normals (nx, nt, ntrials)."""
         ctx = self._sync_device(need_lfp=False)

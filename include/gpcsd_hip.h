@@ -398,6 +398,44 @@ int gpcsd_device_buffer(gpcsd_ctx *ctx, const char *name, unsigned long long *de
 int gpcsd_sample_prior(gpcsd_ctx *ctx, const gpcsd_hparams *hp, int which,
                        const double *normals, int ntrials, double *out);
 
+/* Standard normals from the device generator (no reference counterpart: the reference draws with numpy.random on the host,
+ * gpcsd1d.py:300, gpcsd2d.py:341): out[k] = normal number first + k of stream `stream` under `seed`, k < count.  Philox4x32-10
+ * (Random123) + Box-Muller in fp64: pair i has counter (lo32(i), hi32(i), stream, 0) and key (lo32(seed), hi32(seed)); with the
+ * output words w0..w3, u1 = ((w1 >> 5) 2^26 + (w0 >> 6) + 1/2) 2^-53, u2 likewise from (w3, w2),
+ * normal[2 i] = sqrt(-2 ln u1) cos(2 pi u2), normal[2 i + 1] = sqrt(-2 ln u1) sin(2 pi u2).  Every value is a function of
+ * (seed, stream, index) alone: ranges split differently give the same bits.  One launch, one download; no upload. */
+int gpcsd_normals(gpcsd_ctx *ctx, unsigned long long seed, unsigned stream, unsigned long long first, long count, double *out);
+/* The global index of the first resident trial: a rank of a trial-sharded job (gpcsd_shard_block) passes its block's `first`, and
+ * gpcsd_sample_posterior then draws for its trials the normals the unsharded job draws for them.  gpcsd_set_lfp resets it to 0
+ * (call this after it); gpcsd_dist_set_lfp with replicate = 0 sets every device's to its block's `first`. */
+int gpcsd_set_trial_offset(gpcsd_ctx *ctx, long first);
+/* Joint draws from the POSTERIOR of the CSD / LFP at sites z and ARBITRARY times tstar, nsamples per resident trial -- of the model
+ * whose mean gpcsd_predict_at and whose variance gpcsd_predict_var return (no jitter; a per-electrode noise list on the eigen-index
+ * as utility_functions.py:54-63; the LFP is the noise-free potential).  NO REFERENCE COUNTERPART: the reference has sample_prior only
+ * (gpcsd1d.py:295-309, gpcsd2d.py:336-360).  Matheron's rule: sample = f_prior + P (y_r - phi - eps) with (f_prior, phi) a joint
+ * prior draw Fs Xi Ft^T of the stacked rows [CSD(z) if type & 1; LFP(z) if type & 2; LFP(x)] (ns rows) over the stacked times
+ * [t*; t] (ntt = ntstar + nt columns), eps = Qs diag(sqrt(sig2n)) E a noise draw, P the linear map of gpcsd_predict_at.  The factors
+ * Fs, Ft come from the symmetric eigensolver (negative eigenvalues of rounding size count as zero; the joint covariances are singular
+ * whenever z holds electrodes or t* training times), the spatial one after equilibration to a unit diagonal.  Each draw has the mean
+ * of gpcsd_predict_at and the full posterior covariance; the component SUM only (a joint draw does not identify the components).
+ * Outputs (either may be NULL): (nz, ntstar, ntrials, nsamples), C order.
+ * normals_xi (ntrials, nsamples, ns, ntt) and normals_eps (ntrials, nsamples, nx, nt): host-supplied standard normals -- both or
+ * neither (rc -3).  Both NULL: the device generator (gpcsd_normals) with `seed`, stream 0 for Xi and stream 1 for E, the index of
+ * an entry its C-order index in those arrays with the GLOBAL trial index (gpcsd_set_trial_offset): the same seed gives the same
+ * draws however the call is chunked or sharded.  The draws are processed in chunks of pseudo-trials (trial, draw) whose scratch fits
+ * GPCSD_SAMPLE_SCRATCH_MB megabytes (default 2048; read per call).
+ * rc -3: bad arguments, nsamples < 1, a user-defined temporal covariance (GPCSD_KIND_HOST: no joint Gram over [t*; t] on the
+ * device); GPCSD_ERR_CAPACITY: ns or ntt beyond GPCSD_MAX_EIG_N (checked before z or tstar is read); rc -4 without resident data. */
+int gpcsd_sample_posterior(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double *z, int nz,
+                           const double *tstar, int ntstar, int type, int nsamples, unsigned long long seed,
+                           const double *normals_xi, const double *normals_eps, double *csd, double *lfp);
+/* Same computation (no reference counterpart), results left in the named device buffers "post_sample_csd", "post_sample_lfp"
+ * (nz*ntstar*ntrials*nsamples each) for gpcsd_fetch / gpcsd_device_buffer.  Waits for its own work: a numerical failure (rc > 0) is
+ * returned by the call itself.  The buffers of the posterior means, variances and leave-one-out scores are left alone. */
+int gpcsd_sample_posterior_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double *z, int nz,
+                                    const double *tstar, int ntstar, int type, int nsamples, unsigned long long seed,
+                                    const double *normals_xi, const double *normals_eps);
+
 /* Per-trial whitened quadratic forms  out[b] = sum( (Qs^T resid_b Qt)^2 / Dvec )  for nb residual matrices at once, given a
  * cached decomposition (Qs, Qt, Dvec) from gpcsd_eig_D.  resid is (nx, nt, nb) C-order like lfp.  This is the projection
  * kernel of loglik (gpcsd1d.py:124-127) exposed for downstream per-trial consumers, e.g. the shift-optimisation objective
@@ -572,6 +610,9 @@ int gpcsd_potrf_gate_timeouts(gpcsd_ctx *ctx, long *count);
 int gpcsd_potrf_diag_probe(gpcsd_ctx *ctx, double *out10);
 /* streaming copy microbenchmark over `bytes` bytes: measured GB/s (read+write counted) */
 int gpcsd_hbm_copy_peak(gpcsd_ctx *ctx, long bytes, double *gbs);
+/* the device generator of gpcsd_normals alone: `count` normals into a device buffer, `reps` launches between two events, nothing
+ * copied out; measured GB/s of normals WRITTEN (the copy peak above counts its reads too: compare with half of it) */
+int gpcsd_normals_bench(gpcsd_ctx *ctx, long count, int reps, double *gbs);
 
 #ifdef __cplusplus
 }
