@@ -171,6 +171,10 @@ SIGNATURES = {
     "gpcsd_loo": (_I, [_P, ctypes.POINTER(HParams), _DP, _DP, _DP, _DP]),
     "gpcsd_loo_resident": (_I, [_P, ctypes.POINTER(HParams), _I]),
     "gpcsd_loo_contract": (_I, [_P, _DP, _DP, _DP, _DP, _I, _I, _I, _I, _DP, _DP, _DP]),
+    "gpcsd_analytic": (_I, [_P, _DP, _I, _I, _L, _DP, _DP, _I, _DP, _DP, _DP, _DP]),
+    "gpcsd_analytic_resident": (_I, [_P, ctypes.c_char_p, _L, _I, _I, _L, _DP, _DP, _I, _I]),
+    "gpcsd_plv": (_I, [_P, _DP, _DP, _I, _I, _I, _I, _DP, _DP, _DP]),
+    "gpcsd_plv_resident": (_I, [_P, _I, _I, _I, _I]),
     "gpcsd_fetch": (_I, [_P, ctypes.c_char_p, _DP, _L]),
     "gpcsd_device_buffer": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
     "gpcsd_sample_prior": (_I, [_P, ctypes.POINTER(HParams), _I, _DP, _I, _DP]),
@@ -349,8 +353,11 @@ pinned_pool = PinnedPool()
 class DeviceArray:
     """A float64 C-contiguous view of library-owned device memory (`__cuda_array_interface__` version 3)."""
 
-    def __init__(self, ptr, shape, owner, name=None):
+    def __init__(self, ptr, shape, owner, name=None, base=None):
         self.ptr, self.shape, self._owner, self.name = int(ptr), tuple(shape), owner, name   # (the context stays alive with the view)
+        # the named buffer the view lies in and its first element there, in doubles: what a call that takes a resident source by
+        # name and offset needs (Context.analytic_resident); None for a view of memory the library has no name for
+        self.base = base if base is not None else ((name, 0) if name is not None else None)
         self.__cuda_array_interface__ = {"shape": self.shape, "typestr": "<f8", "data": (self.ptr, False), "version": 3,
                                          "strides": None, "stream": None}
 
@@ -360,7 +367,8 @@ class DeviceArray:
         if not self.shape or not (0 <= i < self.shape[0]):
             raise IndexError(i)
         sub = self.shape[1:]
-        return DeviceArray(self.ptr + 8 * i * int(np.prod(sub)), sub, self._owner, None)
+        n = i * int(np.prod(sub))
+        return DeviceArray(self.ptr + 8 * n, sub, self._owner, None, None if self.base is None else (self.base[0], self.base[1] + n))
 
     def torch(self, device=None):
         import torch
@@ -390,6 +398,7 @@ class Context:
         self._h = h
         self.device = int(device)
         self._keep = []
+        self.phasor_generation = 0       # analytic_resident calls so far: whose unit phasors "phasor_re" / "phasor_im" hold
 
     def close(self):
         if getattr(self, "_h", None):
@@ -963,6 +972,68 @@ class Context:
         self._check(self._lib.gpcsd_loo_contract(self._h, _ptr(V), _ptr(Qt), _ptr(c), _ptr(Y), nx, int(R), nt, K, _ptr(mean), _ptr(lpd),
                                                  _ptr(sse)))
         return mean, lpd, sse
+
+    # ---- band phase and phase locking (phase.hip) ----
+    ANALYTIC_OUTPUTS = (("phase", "phase_out"), ("amp", "phase_amp"), ("u_re", "phasor_re"), ("u_im", "phasor_im"))
+
+    @staticmethod
+    def _operator_parts(A, nts):
+        A = np.asarray(A)
+        if A.ndim != 2 or A.shape[1] != nts or A.shape[0] < 1:
+            raise ValueError("the operator must be (nsel, %d), got %s" % (nts, A.shape))
+        return np.ascontiguousarray(A.real, dtype=np.float64), np.ascontiguousarray(A.imag, dtype=np.float64)
+
+    @classmethod
+    def _analytic_mask(cls, want):
+        names = [k for k, _ in cls.ANALYTIC_OUTPUTS]
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(w not in names for w in want):
+            raise ValueError("want must name at least one of %s" % (names,))
+        return sum(1 << names.index(w) for w in set(want))
+
+    def analytic(self, x, A, want=("phase",)):
+        """Analytic signal of the host array x (nz, nts, M) under the complex operator A (nsel, nts) (gpcsd_analytic): dict with the
+        wanted ones of "phase", "amp", "u_re", "u_im", each (nz, nsel, M); the others are not computed into memory."""
+        x = _arr(x)
+        if x.ndim != 3:
+            raise ValueError("analytic: x must be (nz, nts, M)")
+        nz, nts, M = x.shape
+        Are, Aim = self._operator_parts(A, nts)
+        mask = self._analytic_mask(want)
+        out = {k: pinned_pool.empty((nz, Are.shape[0], M)) if mask & (1 << i) else None for i, (k, _) in enumerate(self.ANALYTIC_OUTPUTS)}
+        self._check(self._lib.gpcsd_analytic(self._h, _ptr(x), nz, nts, M, _ptr(Are), _ptr(Aim), Are.shape[0], _ptr(out["phase"]),
+                                             _ptr(out["amp"]), _ptr(out["u_re"]), _ptr(out["u_im"])))
+        return {k: v for k, v in out.items() if v is not None}
+
+    def analytic_resident(self, src_name, src_offset, shape, A, want=("phase",)):
+        """The same on the named device buffer `src_name` from `src_offset` doubles on, read as shape = (nz, nts, M)
+        (gpcsd_analytic_resident); the wanted outputs stay in "phase_out", "phase_amp", "phasor_re", "phasor_im" -- returned as
+        zero-copy views (nz, nsel, M)."""
+        nz, nts, M = (int(v) for v in shape)
+        Are, Aim = self._operator_parts(A, nts)
+        mask = self._analytic_mask(want)
+        self._check(self._lib.gpcsd_analytic_resident(self._h, src_name.encode(), int(src_offset), nz, nts, M, _ptr(Are), _ptr(Aim),
+                                                      Are.shape[0], mask))
+        self.phasor_generation += 1          # (model_base.plv forms a type's phasors again if another call has replaced them)
+        return {k: self.device_array(buf, (nz, Are.shape[0], M)) for i, (k, buf) in enumerate(self.ANALYTIC_OUTPUTS) if mask & (1 << i)}
+
+    def plv(self, u_re, u_im, want_c=True):
+        """PLV of all site pairs from host unit phasors (nz, nsel, R, S) (gpcsd_plv): (c_re, c_im, plv), each (S, nsel, nz, nz);
+        want_c=False skips the two parts of the mean resultant (None)."""
+        u_re, u_im = _arr(u_re), _arr(u_im)
+        if u_re.ndim != 4 or u_re.shape != u_im.shape:
+            raise ValueError("plv: u_re and u_im must both be (nz, nsel, R, S)")
+        nz, nsel, R, S = u_re.shape
+        c_re, c_im = (np.empty((S, nsel, nz, nz)), np.empty((S, nsel, nz, nz))) if want_c else (None, None)
+        out = np.empty((S, nsel, nz, nz))
+        self._check(self._lib.gpcsd_plv(self._h, _ptr(u_re), _ptr(u_im), nz, nsel, R, S, _ptr(c_re), _ptr(c_im), _ptr(out)))
+        return c_re, c_im, out
+
+    def plv_resident(self, nz, nsel, R, S=1):
+        """The same on the phasors analytic_resident left in "phasor_re" / "phasor_im" (gpcsd_plv_resident): zero-copy views
+        (c_re, c_im, plv) of "plv_re", "plv_im", "plv_abs", each (S, nsel, nz, nz)."""
+        self._check(self._lib.gpcsd_plv_resident(self._h, int(nz), int(nsel), int(R), int(S)))
+        return tuple(self.device_array(b, (int(S), int(nsel), int(nz), int(nz))) for b in ("plv_re", "plv_im", "plv_abs"))
 
     def fetch(self, name, shape):
         out = pinned_pool.empty(shape)

@@ -216,6 +216,9 @@ struct gpcsd_ctx {
     double *d_lfp = nullptr;                // [x][r][t]
     long trial_offset = 0;                  // global index of the first resident trial (gpcsd_set_trial_offset): a rank's block of a
                                             // trial-sharded job draws the normals the unsharded job would (gpcsd_sample_posterior)
+    // shape (nz, nsel, M) of the unit phasors the last gpcsd_analytic_resident left in "phasor_re" / "phasor_im" (0: none, or only
+    // one of the two): what gpcsd_plv_resident may read
+    long phasor_shape[3] = {0, 0, 0};
     gpcsd::SymDev sym_s, sym_t;             // reflection symmetry of the electrode / time grids (ns == 0: none found)
     // folded-basis GEMMs (capi.hip): what the electrode symmetry reflects about, host copies of the grids to recognise
     // prediction sites / times with the same symmetry, the symmetry of the last prediction sites, and whether the

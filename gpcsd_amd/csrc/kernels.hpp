@@ -146,6 +146,30 @@ struct LooDesc {
 void gemm_loo(gpcsd_ctx *c, const LooDesc &d, hipStream_t s);
 void k_loo_var(gpcsd_ctx *c, const double *cdiag, double *var, long n, hipStream_t s);      // var = 1 / cdiag elementwise
 
+// ---------------------------------------------------------------- band phase and phase locking (phase.hip)
+// Analytic signal of X[z][t][m] under the complex operator A = Are + i Aim (nsel, nts) -- band-pass + Hilbert along t as one matrix,
+// rows = the kept times -- with its nonlinear functions in the epilogue: Re/Im[z][j][m] = sum_t Are/Aim[j][t] X[z][t][m] (never
+// stored), amp = hypot(Re, Im), phase = atan2(Im, Re), unit phasor (Re, Im) / amp; amp == 0 gives phase 0 and phasor (1, 0).
+// Outputs in the layout [z][j][m]; a null output is not stored.
+struct AnalyticDesc {
+    const double *X = nullptr;      // (nz, nts, M)
+    int nz = 0, nts = 0;
+    long M = 0;
+    const double *Are = nullptr, *Aim = nullptr;      // (nsel, nts) row-major
+    int nsel = 0;
+    double *phase = nullptr, *amp = nullptr, *ure = nullptr, *uim = nullptr;
+};
+void k_analytic(gpcsd_ctx *c, const AnalyticDesc &d, hipStream_t s);
+// Complex mean resultant over the R trials and its modulus for all site pairs, per (draw s, time j), phasors u = ure + i uim in the
+// layout (nz, nsel, R, S):  cre + i cim = 1/R sum_r u_a conj(u_b),  plv = |.|; outputs (S, nsel, nz, nz), a null one is not stored.
+// Hermitian bit for bit (lower tiles computed, mirror images written from the same registers); fixed summation order, no atomics.
+struct PlvDesc {
+    const double *ure = nullptr, *uim = nullptr;
+    int nz = 0, nsel = 0, R = 0, S = 1;
+    double *cre = nullptr, *cim = nullptr, *plv = nullptr;
+};
+void k_plv(gpcsd_ctx *c, const PlvDesc &d, hipStream_t s);
+
 // ---------------------------------------------------------------- batched hyper-parameter sets
 // Device image of gpcsd_hparams for batched evaluations (gpcsd_loglik_grad_batch): one entry per hyper-parameter set.  The
 // Gram builders / derivative kernels take an optional table: with `tab` they run once for all B sets (the set index is a grid

@@ -860,6 +860,91 @@ class GPCSDModel:
             total = float(sh.allreduce_sum(np.array([total]))[0])
         return total
 
+    @staticmethod
+    def _types(type):
+        if type not in ("csd", "lfp", "both"):
+            raise ValueError("type must be 'csd', 'lfp' or 'both'")
+        return ("csd", "lfp") if type == "both" else (type,)
+
+    def phase(self, A, type="csd", component=None, at=None, resident=False):
+        """Band phase and amplitude of the model's CURRENT prediction along time, at every site and (local) trial: the analytic
+        signal of `csd_pred` / `lfp_pred` -- or of temporal component `component` of their `*_list` forms -- under the operator A
+        (nsel, ntpred) of `utility_functions.analytic_operator` (zero-phase band-pass + Hilbert transform as one matrix; its rows are
+        the kept times).  Works on what the last `predict` / `predict_at` / `loglik_predict_many` left, host arrays or resident
+        views alike; a resident prediction is read in HBM and never crosses PCIe.  Sets `csd_phase`, `csd_amp` and / or
+        `lfp_phase`, `lfp_amp`, each (nz, nsel, ntrials) -- host arrays, or with resident=True (resident predictions, one type per
+        call: the library has one set of result buffers) zero-copy device views -- and `t_phase`: `t_pred` at the kept times when
+        the caller passes the `at` the operator was built with, None otherwise.  The unit phasors are kept for `plv()`.  The
+        prediction, variance, leave-one-out and sample attributes are left alone.  What the reference's scripts do on the host
+        with filtfilt + hilbert + np.angle (auditory_lfp/fit_gpcsd_baseline.py:303-334, neuropixels/fit_gpcsd2d.py:147-159); no
+        counterpart in the package."""
+        from .utility_functions import band_phase
+        types = self._types(type)
+        A = np.asarray(A)
+        if resident and len(types) > 1:
+            raise ValueError("resident=True holds one field's results: call phase() per type")
+        ctx = self._context()
+        keep = dict(getattr(self, "_phasors", {}))
+        for name in types:
+            x = getattr(self, name + "_pred", None)
+            if x is None:
+                raise RuntimeError("phase: no %s prediction to work on (call predict / predict_at with type=%r first)" % (name, name))
+            if component is not None:
+                lst = getattr(self, name + "_pred_list")
+                if not 0 <= int(component) < len(lst):
+                    raise ValueError("component must be in [0, %d)" % len(lst))
+                x = lst[int(component)]
+            dev = isinstance(x, _hip.DeviceArray)
+            if resident and not dev:
+                raise ValueError("resident=True needs a resident prediction")
+            res = band_phase(x, A, want=("phase", "amp", "u_re", "u_im"), resident=dev, ctx=ctx)
+            if dev:
+                # the phasors stay in the library's buffers; plv() forms them again from the source should a later call have
+                # overwritten them (one product, no PCIe)
+                keep[name] = {"source": x, "A": A, "generation": ctx.phasor_generation, "shape": tuple(res["u_re"].shape)}
+                if not resident:
+                    res = {k: ctx.fetch(v.name, v.shape) for k, v in res.items() if k in ("phase", "amp")}
+            else:
+                keep[name] = {"u": (res["u_re"], res["u_im"]), "shape": tuple(res["u_re"].shape)}
+            setattr(self, name + "_phase", res["phase"])
+            setattr(self, name + "_amp", res["amp"])
+        self._phasors = keep
+        self.t_phase = None if at is None else np.asarray(self.t_pred)[np.asarray(at, dtype=np.intp).reshape(-1)]
+
+    def plv(self, type="csd"):
+        """Phase-locking value of all site pairs over the trials, from the phases of the last `phase()` call: sets `csd_plv` /
+        `lfp_plv` (nsel, nz, nz), plv[j, a, b] = |mean over trials of exp(i (phase_a - phase_b))| at kept time j, and
+        `csd_plv_angle` / `lfp_plv_angle`, the angle of that mean resultant (the mean phase difference a - b).  One launch for all
+        pairs and times; plv is symmetric and the angle antisymmetric bit for bit.  Under trial sharding each rank forms the sums
+        R_local * c of its block of trials, the sums are added over the ranks (one all-reduce per type) and every rank holds the
+        PLV over all trials; `gather_predictions` does not apply.  The prediction, variance, leave-one-out and sample attributes
+        are left alone.  No reference counterpart in the package (auditory_lfp/fit_gpcsd_baseline.py:303-334 loops over the pairs)."""
+        from .utility_functions import band_phase, plv, plv_from_sums
+        types = self._types(type)
+        sh = getattr(self, "_sharding", None)
+        if sh is not None and getattr(sh, "gather_predictions", False):
+            raise NotImplementedError("plv: gather_predictions does not apply; each rank works on its block of trials")
+        ctx = self._context()
+        for name in types:
+            rec = getattr(self, "_phasors", {}).get(name)
+            if rec is None:
+                raise RuntimeError("plv: call phase(A, type=%r) first" % name)
+            if "u" in rec:
+                u = rec["u"]
+            else:
+                if rec["generation"] == ctx.phasor_generation:
+                    u = tuple(ctx.device_array(b, rec["shape"]) for b in ("phasor_re", "phasor_im"))
+                else:
+                    u = band_phase(rec["source"], rec["A"], want=("u_re", "u_im"), resident=True)
+                    rec["generation"] = ctx.phasor_generation
+            p, c = plv(u, ctx=ctx)
+            if sh is not None:
+                R_local = rec["shape"][2]
+                sums = sh.allreduce_sum(np.stack([R_local * c.real, R_local * c.imag]))
+                p, c = plv_from_sums(sums, np.atleast_3d(self.lfp).shape[2])
+            setattr(self, name + "_plv", p)
+            setattr(self, name + "_plv_angle", np.arctan2(c.imag, c.real))
+
     def loglik_predict_many(self, param_sets, z, t, type="csd", resident=False, share_spatial=False):
         """loglik() and predict(z, t, type) under each of a LIST of hyper-parameter sets -- dicts as extract_model_params() returns
         them: the optima of every restart of a fit, a grid, posterior draws -- in order.  Returns the log-likelihoods, one per set;

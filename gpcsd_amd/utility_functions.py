@@ -2,7 +2,9 @@
 
 Mirrors src/gpcsd/utility_functions.py: normalize :7-8, sort_grid :10-13, expand_grid :15-23, reduce_grid
 :25-33, mykron :35-42 (API parity only -- never on the fast path), comp_eig_D :44-64 (two HIP symmetric
-eigendecompositions + the D vector)."""
+eigendecompositions + the D vector).  analytic_operator, band_phase, plv, plv_from_sums have no counterpart in the package: they are
+the band-pass + Hilbert + phase-locking step the reference's analysis scripts end with, as one linear operator (host) and two HIP
+launches (csrc/phase.hip)."""
 import numpy as np
 
 from . import _hip
@@ -56,6 +58,116 @@ def whitened_quadratic_forms(evec_s, evec_t, Dvec, resid):
     batched over trials on the GPU."""
     from . import _hip
     return _hip.default_context().whitened_quad(evec_s, evec_t, Dvec, resid)
+
+
+def analytic_operator(n, sos=None, ba=None, at=None, **filter_kwargs):
+    """The complex matrix A (nsel, n), complex128, of "zero-phase band-pass, then analytic signal" along a time axis of length n:
+    `A @ x == scipy.signal.hilbert(filt(x))` with filt = `scipy.signal.sosfiltfilt(sos, .)`, `scipy.signal.filtfilt(b, a, .)` for
+    ba = (b, a), or nothing (pure Hilbert transform).  Both steps are linear in the signal for a fixed length (the filters'
+    edge padding and initial conditions included), so the operator is their action on the n x n identity along axis 0;
+    filter_kwargs (padtype, padlen, ...) go to the filter call.  at: time indices to keep, in any order (default: all) -- keeping a
+    time is keeping a row.  Filter design stays with the caller (scipy.signal.butter ...), as in the reference's scripts
+    (auditory_lfp/fit_gpcsd_baseline.py:303-334, neuropixels/fit_gpcsd2d.py:147-159).
+
+    Prefer `sos` for narrow bands: the operator reproduces the direct call to 1e-14 of the largest entry with second-order
+    sections, but only to about 1e-8 for an order-3 transfer-function (b, a) band-pass of 8-12 Hz at 1 kHz over 100 samples --
+    that is the conditioning of the (b, a) form itself (the two calls, each as good as the other, differ by that much)."""
+    import scipy.signal
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be at least 1")
+    if sos is not None and ba is not None:
+        raise ValueError("give sos or ba, not both")
+    F = np.eye(n)
+    if sos is not None:
+        F = scipy.signal.sosfiltfilt(sos, F, axis=0, **filter_kwargs)
+    elif ba is not None:
+        F = scipy.signal.filtfilt(ba[0], ba[1], F, axis=0, **filter_kwargs)
+    elif filter_kwargs:
+        raise ValueError("filter arguments without a filter: %s" % sorted(filter_kwargs))
+    A = scipy.signal.hilbert(F, axis=0)
+    if at is not None:
+        A = A[np.asarray(at, dtype=np.intp).reshape(-1)]
+    return np.ascontiguousarray(A, dtype=np.complex128)
+
+
+def band_phase(x, A, want=("phase",), resident=False, ctx=None):
+    """Band phase along the time axis of x (nz, n, M) or (nz, n, R, S) -- a NumPy array, or a `_hip.DeviceArray` such as a resident
+    prediction (`m.csd_pred`, `m.csd_pred_list[c]`) or resident posterior draws -- under the operator A (nsel, n) of
+    `analytic_operator`: dict with the wanted ones of "phase" (atan2), "amp" (hypot), "u_re", "u_im" (the unit phasor; (1, 0) and
+    phase 0 where amp == 0), each shaped like x with n -> nsel.  One fp64 MFMA product with the nonlinear functions in its epilogue;
+    outputs not asked for are not stored.  A device input is read where it lies (no copy over PCIe); with resident=True its results
+    are zero-copy views of the library's buffers "phase_out", "phase_amp", "phasor_re", "phasor_im" (valid until the next call that
+    writes them), otherwise host arrays.  ctx: the `_hip.Context` a host input is sent to (default: the process-wide one; a device
+    input brings its own).  No reference counterpart."""
+    A = np.asarray(A)
+    shape = tuple(int(v) for v in x.shape)
+    if len(shape) not in (3, 4):
+        raise ValueError("x must be (nz, n, M) or (nz, n, R, S)")
+    nz, n = shape[:2]
+    M = int(np.prod(shape[2:]))
+    out_shape = (nz, A.shape[0]) + shape[2:]
+    if isinstance(x, _hip.DeviceArray):
+        if x.base is None:
+            raise ValueError("band_phase: the device array is not a view of a named buffer of the library")
+        ctx = x._owner
+        res = ctx.analytic_resident(x.base[0], x.base[1], (nz, n, M), A, want)
+        if resident:
+            return {k: _hip.DeviceArray(v.ptr, out_shape, ctx, v.name) for k, v in res.items()}
+        return {k: ctx.fetch(v.name, out_shape) for k, v in res.items()}
+    if resident:
+        raise ValueError("resident=True needs a device input")
+    res = (ctx or _hip.default_context()).analytic(np.asarray(x, dtype=np.float64).reshape(nz, n, M), A, want)
+    return {k: v.reshape(out_shape) for k, v in res.items()}
+
+
+def plv_from_sums(sums, ntrials):
+    """(plv, c) from sum_r u_a conj(u_b) over `ntrials` trials, given as a complex array or as the stacked pair (2, ...) of its real
+    and imaginary parts -- the host-side combine of a trial-sharded job: every rank forms R_local * c of its block, the sums add."""
+    sums = np.asarray(sums)
+    if not np.iscomplexobj(sums):
+        sums = sums[0] + 1j * sums[1]
+    c = sums / float(ntrials)
+    return np.abs(c), c
+
+
+def plv(phasors_or_phase, resident=False, ctx=None):
+    """Phase-locking value of ALL site pairs over the trials.  Input: the dict `band_phase` returns (with "u_re" and "u_im"), a pair
+    (u_re, u_im), or a host array of phases (cos / sin are then formed on the host), each array (nz, nsel, R) or (nz, nsel, R, S)
+    with S draws per trial.  Returns (plv, c): plv[j, a, b] = |c[j, a, b]|, c[j, a, b] = mean over the trials of
+    exp(i (phase_a - phase_b)) at kept time j -- the complex mean resultant, whose angle is the mean phase difference -- of shape
+    (nsel, nz, nz), or (S, nsel, nz, nz) for a four-dimensional input.  One launch for all pairs, times and draws; plv and c.real
+    are symmetric and c.imag antisymmetric bit for bit, and the same call gives the same bits.  Phasors that are resident views
+    (band_phase(..., resident=True)) are read where they lie; resident=True then returns zero-copy views (plv, (c_re, c_im))
+    instead of host arrays.  ctx as in band_phase.  No reference counterpart."""
+    if isinstance(phasors_or_phase, dict):
+        u_re, u_im = phasors_or_phase["u_re"], phasors_or_phase["u_im"]
+    elif isinstance(phasors_or_phase, (tuple, list)):
+        u_re, u_im = phasors_or_phase
+    else:
+        ph = np.asarray(phasors_or_phase, dtype=np.float64)
+        u_re, u_im = np.cos(ph), np.sin(ph)
+    shape = tuple(int(v) for v in u_re.shape)
+    if len(shape) not in (3, 4) or tuple(u_im.shape) != shape:
+        raise ValueError("the phasors must be two arrays of one shape, (nz, nsel, R) or (nz, nsel, R, S)")
+    nz, nsel, R = shape[:3]
+    S = shape[3] if len(shape) == 4 else 1
+    out_shape = (S, nsel, nz, nz) if len(shape) == 4 else (nsel, nz, nz)
+    if isinstance(u_re, _hip.DeviceArray) or isinstance(u_im, _hip.DeviceArray):
+        if getattr(u_re, "name", None) != "phasor_re" or getattr(u_im, "name", None) != "phasor_im":
+            raise ValueError("device phasors must be the views band_phase(..., resident=True) returned")
+        ctx = u_re._owner
+        views = ctx.plv_resident(nz, nsel, R, S)
+        if resident:
+            c_re, c_im, p = (_hip.DeviceArray(v.ptr, out_shape, ctx, v.name) for v in views)
+            return p, (c_re, c_im)
+        c_re, c_im, p = (ctx.fetch(v.name, out_shape) for v in views)
+    else:
+        if resident:
+            raise ValueError("resident=True needs device phasors")
+        c_re, c_im, p = (v.reshape(out_shape) for v in (ctx or _hip.default_context()).plv(
+            np.asarray(u_re, dtype=np.float64).reshape(nz, nsel, R, S), np.asarray(u_im, dtype=np.float64).reshape(nz, nsel, R, S)))
+    return p, c_re + 1j * c_im
 
 
 def fit_trial_shifts(evec_s, evec_t, Dvec, lfp_trials, mu_lfp, t, tau0=None, mutau=0.0, sigtau=10.0, width=None,

@@ -376,6 +376,47 @@ int gpcsd_loo_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, int want_mean);
  * anything is read. */
 int gpcsd_loo_contract(gpcsd_ctx *ctx, const double *V, const double *Qt, const double *c, const double *Y, int nx, int R, int nt,
                        int K, double *mean, double *lpd, double *sse);
+/* Band phase of a field along time: the analytic signal under a complex operator A = A_re + i A_im (nsel, nts) -- a zero-phase
+ * band-pass (filtfilt / sosfiltfilt) followed by the Hilbert transform along an axis of fixed length is ONE such matrix, keeping a
+ * few times keeps those rows (gpcsd_amd.utility_functions.analytic_operator builds it; filter design stays the caller's) -- and its
+ * amplitude, phase and unit phasor.  NO REFERENCE COUNTERPART in the package; usage note: it replaces the filtfilt + hilbert +
+ * np.angle passes over csd_pred that the reference's analysis scripts end with (auditory_lfp/fit_gpcsd_baseline.py:303-334,
+ * neuropixels/fit_gpcsd2d.py:147-159).  x (nz, nts, M), M innermost (the trials, or (trial, draw) flattened):
+ *   Re[z, j, m] = sum_t A_re[j, t] x[z, t, m],   Im likewise from A_im                      (one fp64 MFMA product, never stored)
+ *   amp = hypot(Re, Im),   phase = atan2(Im, Re),   (u_re, u_im) = (Re, Im) / amp;          amp == 0: phase 0, phasor (1, 0)
+ * Outputs (nz, nsel, M) each; any may be NULL and is then neither computed into memory nor touched.  Host arrays: upload, one
+ * launch, download.  rc -3: NULL inputs or an empty shape; GPCSD_ERR_CAPACITY (before anything is read): M >=
+ * GPCSD_MAX_GEMM_LD_KMAJOR, nts >= 2^22, nz * M >= 2^31. */
+int gpcsd_analytic(gpcsd_ctx *ctx, const double *x, int nz, int nts, long M, const double *A_re, const double *A_im, int nsel,
+                   double *phase, double *amp, double *u_re, double *u_im);
+/* Same computation (no reference counterpart; usage note as gpcsd_analytic) on a field that is ALREADY in HBM: the named ctx-owned
+ * device buffer src_name ("pred_out_csd", "pred_out_lfp", their "_list" forms, "post_sample_csd", "post_sample_lfp", ...) from
+ * src_offset doubles on (component c of a "_list" buffer: c * nz * nts * M), read as (nz, nts, M).  want_mask: bit 0 phase -> "phase_out",
+ * bit 1 amp -> "phase_amp", bit 2 u_re -> "phasor_re", bit 3 u_im -> "phasor_im" (nz * nsel * M doubles each, for gpcsd_fetch /
+ * gpcsd_device_buffer / gpcsd_plv_resident); outputs not asked for are not stored.  Collects a queued prediction's deferred status
+ * first (rc > 0 as gpcsd_fetch), waits for its own work and leaves every other buffer alone.  rc -2: no buffer of that name; rc -3:
+ * bad arguments, the source is one of the outputs, or it holds fewer than src_offset + nz * nts * M doubles; capacity as
+ * gpcsd_analytic. */
+int gpcsd_analytic_resident(gpcsd_ctx *ctx, const char *src_name, long src_offset, int nz, int nts, long M, const double *A_re,
+                            const double *A_im, int nsel, int want_mask);
+/* Phase-locking value of ALL site pairs over the trials, from unit phasors u = u_re + i u_im (nz, nsel, R, S): R trials, S draws per
+ * trial with the draw index innermost (S = 1 for posterior means; gpcsd_sample_posterior's layout otherwise).  NO REFERENCE
+ * COUNTERPART in the package; usage note: one launch in place of the Python loop over site pairs of
+ * auditory_lfp/fit_gpcsd_baseline.py:303-334.  For every draw s and kept time j,
+ *   c_re[s, j, a, b] = 1/R sum_r (u_re[a] u_re[b] + u_im[a] u_im[b])            the complex mean resultant of exp(i (phi_a - phi_b)):
+ *   c_im[s, j, a, b] = 1/R sum_r (u_im[a] u_re[b] - u_re[a] u_im[b])            its angle is the mean phase difference, and the
+ *   plv[s, j, a, b]  = hypot(c_re, c_im)                                         ranks of a trial-sharded job add R c
+ * Outputs (S, nsel, nz, nz) each, any may be NULL.  Only the tiles on or below the diagonal are computed and their mirror images are
+ * written from the same registers: plv and c_re are symmetric, c_im antisymmetric BIT FOR BIT, the diagonal of c_im is 0.  The sums
+ * run in a fixed order without atomics: the same call returns the same bits.  Host arrays: upload, one launch, download.  rc -3: NULL
+ * inputs or an empty shape; GPCSD_ERR_CAPACITY (before anything is read): R * S >= GPCSD_MAX_GEMM_LD_KMAJOR, nz >= 2^21, or 2^31 tiles. */
+int gpcsd_plv(gpcsd_ctx *ctx, const double *u_re, const double *u_im, int nz, int nsel, int R, int S, double *c_re, double *c_im,
+              double *plv);
+/* Same computation (no reference counterpart; usage note as gpcsd_plv) on the unit phasors gpcsd_analytic_resident left in
+ * "phasor_re" / "phasor_im", read as (nz, nsel, R, S); results in the named device buffers "plv_re", "plv_im", "plv_abs"
+ * (S * nsel * nz * nz doubles each).  Waits for its own work and leaves every other buffer alone.  rc -4 unless the last
+ * gpcsd_analytic_resident call stored both halves of the phasors with nz, nsel and M = R * S as given here. */
+int gpcsd_plv_resident(gpcsd_ctx *ctx, int nz, int nsel, int R, int S);
 /* copy `count` doubles of the named ctx-owned device buffer to host; rc -2 if the name is unknown; rc > 0 if the
  * asynchronous gpcsd_predict_resident that produced the buffer failed numerically */
 int gpcsd_fetch(gpcsd_ctx *ctx, const char *name, double *host, long count);
