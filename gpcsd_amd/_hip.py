@@ -175,6 +175,9 @@ SIGNATURES = {
     "gpcsd_analytic_resident": (_I, [_P, ctypes.c_char_p, _L, _I, _I, _L, _DP, _DP, _I, _I]),
     "gpcsd_plv": (_I, [_P, _DP, _DP, _I, _I, _I, _I, _DP, _DP, _DP]),
     "gpcsd_plv_resident": (_I, [_P, _I, _I, _I, _I]),
+    "gpcsd_trsm_lower_trans": (_I, [_P, _DP, _I, _DP, _I, _DP]),
+    "gpcsd_torus_graph": (_I, [_P, _DP, _DP, _I, _I, _DP, _I, _DP, ctypes.POINTER(_I), _DP, _DP, _DP]),
+    "gpcsd_torus_graph_resident": (_I, [_P, ctypes.POINTER(_I), _I, _I, _I, _I, _I, _DP, _I, _DP, ctypes.POINTER(_I), _DP]),
     "gpcsd_fetch": (_I, [_P, ctypes.c_char_p, _DP, _L]),
     "gpcsd_device_buffer": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
     "gpcsd_sample_prior": (_I, [_P, ctypes.POINTER(HParams), _I, _DP, _I, _DP]),
@@ -1034,6 +1037,63 @@ class Context:
         (c_re, c_im, plv) of "plv_re", "plv_im", "plv_abs", each (S, nsel, nz, nz)."""
         self._check(self._lib.gpcsd_plv_resident(self._h, int(nz), int(nsel), int(R), int(S)))
         return tuple(self.device_array(b, (int(S), int(nsel), int(nz), int(nz))) for b in ("plv_re", "plv_im", "plv_abs"))
+
+    # ---- phase-difference torus graph (torus.hip) ----
+    def trsm_lower_trans(self, L, B):
+        """Solve L^T X = B with the lower factor L (gpcsd_trsm_lower_trans); B (n,) or (n, nrhs)."""
+        L = _arr(L)
+        B2 = _arr(np.asarray(B, dtype=np.float64).reshape(L.shape[0], -1))
+        X = np.empty_like(B2)
+        self._check(self._lib.gpcsd_trsm_lower_trans(self._h, _ptr(L), L.shape[0], _ptr(B2), B2.shape[1], _ptr(X)))
+        return X.reshape(np.shape(B))
+
+    @staticmethod
+    def _tg_weights(weights, N):
+        if weights is None:
+            return None, 1
+        w = _arr(np.atleast_2d(np.asarray(weights, dtype=np.float64)))
+        if w.ndim != 2 or w.shape[1] != N or w.shape[0] < 1:
+            raise ValueError("torus_graph: weights must be (B, %d), got %s" % (N, w.shape))
+        return w, w.shape[0]
+
+    @staticmethod
+    def _tg_result(phi, status, chi2, extra=None):
+        res = {"phi": phi, "status": status, "chi2": chi2}
+        res.update(extra or {})
+        return res
+
+    def torus_graph(self, u_re, u_im, weights=None, inference=True, want_gamma=False):
+        """Score-matching fit of the phase-difference torus graph from host unit phasors (d, N) (gpcsd_torus_graph), one fit per row
+        of weights (B, N) (None: one unit-weight fit).  Dict: "phi" (B, P, 2) with NaN rows where "status" (B,) is not 0; "chi2" (P,)
+        of replicate 0 (None without inference); with want_gamma "gamma0" (2P, 2P) and "h0" (2P,) of replicate 0."""
+        u_re, u_im = _arr(u_re), _arr(u_im)
+        if u_re.ndim != 2 or u_re.shape != u_im.shape:
+            raise ValueError("torus_graph: u_re and u_im must both be (d, N)")
+        d, N = u_re.shape
+        w, B = self._tg_weights(weights, N)
+        P = d * (d - 1) // 2
+        phi = np.empty((B, P, 2))
+        status = np.zeros(B, dtype=np.int32)
+        chi2 = np.empty(P) if inference else None
+        gamma0, h0 = (np.empty((2 * P, 2 * P)), np.empty(2 * P)) if want_gamma else (None, None)
+        self._check(self._lib.gpcsd_torus_graph(self._h, _ptr(u_re), _ptr(u_im), d, N, _ptr(w), B, _ptr(phi),
+                                                status.ctypes.data_as(ctypes.POINTER(_I)), _ptr(chi2), _ptr(gamma0), _ptr(h0)))
+        return self._tg_result(phi, status, chi2, {"gamma0": gamma0, "h0": h0} if want_gamma else None)
+
+    def torus_graph_resident(self, sites, j, shape, weights=None, inference=True):
+        """The same on the phasors analytic_resident left in "phasor_re" / "phasor_im", read as shape = (nz, nsel, R): the nodes are
+        the rows `sites` at kept time j (gpcsd_torus_graph_resident).  Results on the host, as torus_graph."""
+        nz, nsel, R = (int(v) for v in shape)
+        sites = np.ascontiguousarray(np.asarray(sites).reshape(-1), dtype=np.int32)
+        d = sites.size
+        w, B = self._tg_weights(weights, R)
+        P = d * (d - 1) // 2
+        phi = np.empty((B, P, 2))
+        status = np.zeros(B, dtype=np.int32)
+        chi2 = np.empty(P) if inference else None
+        self._check(self._lib.gpcsd_torus_graph_resident(self._h, sites.ctypes.data_as(ctypes.POINTER(_I)), d, int(j), nz, nsel, R, _ptr(w),
+                                                         B, _ptr(phi), status.ctypes.data_as(ctypes.POINTER(_I)), _ptr(chi2)))
+        return self._tg_result(phi, status, chi2)
 
     def fetch(self, name, shape):
         out = pinned_pool.empty(shape)

@@ -3,6 +3,7 @@
 // helpers), context and resident data.  The call families themselves are the capi_*.inl parts included at the end.
 #include <functional>
 #include <cmath>
+#include <limits>
 #include <mutex>
 #include <optional>
 
@@ -1412,6 +1413,7 @@ extern "C" int gpcsd_set_time(gpcsd_ctx *c, const double *t, int nt) {
 #include "capi_fused.inl"
 #include "capi_sample.inl"
 #include "capi_phase.inl"
+#include "capi_torus.inl"
 #include "capi_grad.inl"
 #include "capi_measure.inl"
 #include "capi_dist.inl"

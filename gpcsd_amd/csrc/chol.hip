@@ -561,6 +561,44 @@ void trsm_lower_device(gpcsd_ctx *c, const double *L, int n, double *B, int nrhs
     GP_HIP(hipGetLastError());
 }
 
+// L^T X = B in place, by the same inverted-diagonal-block + GEMM scheme run from the last block row upwards: with the inverse
+// Xkk of the diagonal block L_kk, X_blk = Xkk^T B_blk (row block p0 of Xkk^T has its non-zeros in columns p0..: one K-limited
+// product per NB-row block, which also keeps the stale strictly upper part of the inverse buffer out), then
+// B[above] -= L[k0.., 0..k0)^T X_blk.  Both products read their first operand transposed (stored (K, M)).
+void trsm_lower_trans_device(gpcsd_ctx *c, const double *L, int n, double *B, int nrhs, hipStream_t s) {
+    ProfScope ps(c, "trsm_trans", (double)n * n * nrhs, s);
+    double *X = c->buf<double>("chol_Linv", (size_t)NBO * NBO);
+    double *tmp = c->buf<double>("chol_inv_tmp", (size_t)NBO * NBO);
+    double *Xb = c->buf<double>("trsm_xblk", (size_t)NBO * nrhs);
+    auto gemm_ta = [&](int M, int N, int K, const double *A, long lda, const double *Bm, double *C, double alpha, int epi) {
+        GemmDesc g;
+        g.M = M; g.N = N; g.K = K;
+        g.A = A; g.lda = lda; g.transA = true; g.B = Bm; g.ldb = nrhs; g.C = C; g.ldc = nrhs;
+        g.alpha = alpha; g.epi = epi;
+        g.prio = 1;
+        g.prof_name = "trsm_gemm";
+        gemm_f64(c, g, s);
+    };
+    const int last = (n - 1) / NBO * NBO;
+    for (int k0 = last; k0 >= 0; k0 -= NBO) {
+        const int nb = std::min(NBO, n - k0);
+        const double *Lkk = L + (long)k0 * n + k0;
+        for (int p0 = 0; p0 < nb; p0 += NB)
+            launch_diag(const_cast<double *>(Lkk) + (long)p0 * n + p0, (long)n, std::min(NB, nb - p0), X + (long)p0 * NBO + p0, (long)NBO,
+                        nullptr, 0, false, s);
+        assemble_block_inverse(c, Lkk, n, nb, X, tmp, s);
+        for (int p0 = 0; p0 < nb; p0 += NB) {
+            const int b = std::min(NB, nb - p0);
+            gemm_ta(b, nrhs, nb - p0, X + (long)p0 * NBO + p0, NBO, B + (long)(k0 + p0) * nrhs, Xb + (long)p0 * nrhs, 1.0, EPI_STORE);
+        }
+        hipLaunchKernelGGL(copy2d_kernel, dim3(ceil_div((long)nb * nrhs, 256)), dim3(256), 0, s, (const double *)Xb, (long)nrhs,
+                           B + (long)k0 * nrhs, (long)nrhs, nb, nrhs);
+        if (k0 > 0)                                       // B[above] -= L[k0 : k0 + nb, 0 : k0]^T X_blk
+            gemm_ta(k0, nrhs, nb, L + (long)k0 * n, n, Xb, B, -1.0, EPI_ACCUM);
+    }
+    GP_HIP(hipGetLastError());
+}
+
 __global__ __launch_bounds__(256) void logdet_chol_kernel(const double *__restrict__ L, int n, double *out) {
     __shared__ double sh[256];
     double s = 0.0;

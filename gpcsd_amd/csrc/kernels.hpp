@@ -170,6 +170,31 @@ struct PlvDesc {
 };
 void k_plv(gpcsd_ctx *c, const PlvDesc &d, hipStream_t s);
 
+// ---------------------------------------------------------------- phase-difference torus graph (torus.hip)
+// d nodes, N trials; node a's phasors are ure / uim [off[a] .. off[a] + N) (off: device table, so a strided slice of the resident
+// phasors and a dense (d, N) upload are one code path); pi / pj: device tables of the P = d (d - 1) / 2 pairs (i < j) in the order
+// of np.triu_indices(d, 1).  m = 2 P parameters in the interleaved order (2p: cos, 2p + 1: sin).
+constexpr int TG_MAX_NODES = 128;
+constexpr int TG_REPS_PER_WG = 4;          // replicates that share the operand tiles of a node-Gram workgroup
+constexpr double TG_PIVOT_TOL = 64.0;      // a pivot below TG_PIVOT_TOL m u of its diagonal entry is a failed pivot
+struct TgDesc {
+    const double *ure = nullptr, *uim = nullptr;
+    const long *off = nullptr;
+    const int *pi = nullptr, *pj = nullptr;
+    int d = 0, N = 0;
+};
+// G[rep][a] (nv x nv, nv = 2 d - 1, lower part) = 1/W sum_n w[rep][n] v_n(a) v_n(a)^T on MFMA; w == nullptr: unit weights
+void k_tg_node_gram(gpcsd_ctx *c, const TgDesc &t, const double *w, const double *W, int nrep, double *G, hipStream_t s);
+// Gamma[rep] (m x m, symmetric bit for bit, exact zeros between pairs without a common node) and H[rep] (m) gathered from G
+void k_tg_assemble(gpcsd_ctx *c, const TgDesc &t, const double *G, int nrep, double *Gamma, double *H, hipStream_t s);
+void k_tg_diag_save(gpcsd_ctx *c, const double *Gamma, int m, int nrep, double *dg, hipStream_t s);
+// status = first pivot (+ 1) of the factor L whose square is not above TG_PIVOT_TOL m u dg[pivot], merged with potrf's own report
+void k_tg_pivot_check(gpcsd_ctx *c, const double *L, const double *dg, int m, int *status, hipStream_t s);
+// R (m x N) = D_n (D_n^T phi) - 2 S_n per trial; g (d x N) scratch
+void k_tg_residuals(gpcsd_ctx *c, const TgDesc &t, const double *phi, double *g, double *R, hipStream_t s);
+// chi2[p] = phi_p^T Sigma_pp^-1 phi_p with Sigma_pp = 1/W^2 sum_n w_n z_n z_n^T over rows 2p, 2p + 1 of Z (m x N)
+void k_tg_chi2(gpcsd_ctx *c, const double *Z, const double *w, const double *phi, int P, int N, double W, double *chi2, hipStream_t s);
+
 // ---------------------------------------------------------------- batched hyper-parameter sets
 // Device image of gpcsd_hparams for batched evaluations (gpcsd_loglik_grad_batch): one entry per hyper-parameter set.  The
 // Gram builders / derivative kernels take an optional table: with `tab` they run once for all B sets (the set index is a grid
@@ -481,6 +506,8 @@ void potrf_device(gpcsd_ctx *c, double *A, int n, int *d_status, hipStream_t s);
 void potrf_diag128_probe(gpcsd_ctx *c, double *A, int n, double *X, int *d_status, unsigned long long *clk_dev, hipStream_t s);
 // X = L^{-1} B in place (B (n,nrhs) row-major)
 void trsm_lower_device(gpcsd_ctx *c, const double *L, int n, double *B, int nrhs, hipStream_t s);
+// X = L^{-T} B in place (the transposed solve of the same factor; B (n,nrhs) row-major)
+void trsm_lower_trans_device(gpcsd_ctx *c, const double *L, int n, double *B, int nrhs, hipStream_t s);
 void logdet_chol_device(gpcsd_ctx *c, const double *L, int n, double *out, hipStream_t s);
 void sumsq_device(gpcsd_ctx *c, const double *x, long n, double *out, hipStream_t s);
 

@@ -945,6 +945,34 @@ class GPCSDModel:
             setattr(self, name + "_plv", p)
             setattr(self, name + "_plv_angle", np.arctan2(c.imag, c.real))
 
+    def torus_graph(self, type="csd", at=0, sites=None, nboot=0, seed=None):
+        """Phase-difference torus graph (score matching) of the phases of the last `phase()` call at kept time `at`, over the trials:
+        the CONDITIONAL coupling of every pair of `sites` (default: all prediction sites) given the others, where `plv()` is the
+        marginal one.  Sets `csd_tg` / `lfp_tg` to the dict of `utility_functions.torus_graph` (pairs, phi, cond_coupling, chi2, pvals,
+        and with nboot > 0 the bootstrap replicates under `seed`).  Phasors that are resident are gathered and fitted in HBM; only
+        the small results come back.  Needs more trials than a model of d (d - 1) parameters can be fitted to: np.linalg.LinAlgError
+        otherwise.  Trial-sharded models are not supported (fit on the gathered phases with utility_functions.torus_graph).  The
+        prediction, phase, variance, leave-one-out and sample attributes are left alone.  No counterpart in the package
+        (auditory_lfp/torus_graph_fit.py, neuropixels/fit_torus_graph.py)."""
+        from .utility_functions import band_phase, torus_graph
+        types = self._types(type)
+        if getattr(self, "_sharding", None) is not None:
+            raise NotImplementedError("torus_graph: trial-sharded models are out of scope; gather the phases and call utility_functions.torus_graph")
+        ctx = self._context()
+        for name in types:
+            rec = getattr(self, "_phasors", {}).get(name)
+            if rec is None:
+                raise RuntimeError("torus_graph: call phase(A, type=%r) first" % name)
+            if "u" in rec:
+                u = rec["u"]
+            elif rec["generation"] == ctx.phasor_generation:
+                u = tuple(ctx.device_array(b, rec["shape"]) for b in ("phasor_re", "phasor_im"))
+            else:
+                u = band_phase(rec["source"], rec["A"], want=("u_re", "u_im"), resident=True)
+                u = (u["u_re"], u["u_im"])
+                rec["generation"] = ctx.phasor_generation
+            setattr(self, name + "_tg", torus_graph(u, nboot=nboot, seed=seed, ctx=ctx, at=at, sites=sites))
+
     def loglik_predict_many(self, param_sets, z, t, type="csd", resident=False, share_spatial=False):
         """loglik() and predict(z, t, type) under each of a LIST of hyper-parameter sets -- dicts as extract_model_params() returns
         them: the optima of every restart of a fit, a grid, posterior draws -- in order.  Returns the log-likelihoods, one per set;

@@ -4,7 +4,7 @@ Mirrors src/gpcsd/utility_functions.py: normalize :7-8, sort_grid :10-13, expand
 :25-33, mykron :35-42 (API parity only -- never on the fast path), comp_eig_D :44-64 (two HIP symmetric
 eigendecompositions + the D vector).  analytic_operator, band_phase, plv, plv_from_sums have no counterpart in the package: they are
 the band-pass + Hilbert + phase-locking step the reference's analysis scripts end with, as one linear operator (host) and two HIP
-launches (csrc/phase.hip)."""
+launches (csrc/phase.hip); torus_graph, the conditional phase coupling those scripts fit next, likewise (csrc/torus.hip)."""
 import numpy as np
 
 from . import _hip
@@ -168,6 +168,93 @@ def plv(phasors_or_phase, resident=False, ctx=None):
         c_re, c_im, p = (v.reshape(out_shape) for v in (ctx or _hip.default_context()).plv(
             np.asarray(u_re, dtype=np.float64).reshape(nz, nsel, R, S), np.asarray(u_im, dtype=np.float64).reshape(nz, nsel, R, S)))
     return p, c_re + 1j * c_im
+
+
+def _torus_graph_weights(N, weights, nboot, seed):
+    """The replicate weights handed to the library: None (the unit-weight fit alone), or row 0 = ones followed by the bootstrap
+    multiplicities / the caller's rows."""
+    if weights is not None and nboot:
+        raise ValueError("give weights or nboot, not both")
+    if weights is not None:
+        extra = np.atleast_2d(np.asarray(weights, dtype=np.float64))
+        if extra.ndim != 2 or extra.shape[1] != N:
+            raise ValueError("weights must be (B', %d), got %s" % (N, extra.shape))
+    elif nboot:
+        if nboot < 0:
+            raise ValueError("nboot must not be negative")
+        extra = np.random.default_rng(seed).multinomial(N, [1.0 / N] * N, size=int(nboot)).astype(np.float64)
+    else:
+        return None
+    return np.concatenate([np.ones((1, N)), extra], axis=0)
+
+
+def _torus_graph_result(res, d, inference):
+    """The public dict from what `_hip.Context.torus_graph*` returns (replicate 0 = the unit-weight fit)."""
+    import warnings
+    import scipy.special
+    status = np.asarray(res["status"])
+    if status[0] != 0:
+        raise np.linalg.LinAlgError("torus_graph: Gamma is singular (pivot %d of the factorisation failed): fewer trials than the "
+                                    "%d parameters need?" % (status[0] - 1, d * (d - 1)))
+
+    def coupling(phi):
+        k = np.hypot(phi[..., 0], phi[..., 1])
+        return scipy.special.i1e(k) / scipy.special.i0e(k)
+
+    i, j = np.triu_indices(d, 1)
+    phi = res["phi"]
+    out = {"pairs": np.stack([i, j], axis=1), "phi": phi[0], "cond_coupling": coupling(phi[0]),
+           "chi2": res["chi2"] if inference else None, "pvals": np.exp(-0.5 * res["chi2"]) if inference else None}
+    if phi.shape[0] > 1:
+        bad = np.flatnonzero(status[1:])
+        if bad.size:
+            warnings.warn("torus_graph: %d of %d replicates have a singular Gamma and stay NaN (first: %d)" % (bad.size, phi.shape[0] - 1, bad[0]))
+        out.update(phi_boot=phi[1:], cond_coupling_boot=coupling(phi[1:]), status_boot=status[1:].copy())
+    return out
+
+
+def torus_graph(phases_or_phasors, weights=None, nboot=0, seed=None, inference=True, ctx=None, at=0, sites=None):
+    """Phase-difference torus graph of d nodes over N trials by score matching: log p(x) = sum over the pairs p = (i, j), i < j, of
+    phi[p, 0] cos(x_i - x_j) + phi[p, 1] sin(x_i - x_j) -- the CONDITIONAL phase coupling of every pair given all other nodes, where
+    `plv` is the marginal one.  Input as for `plv`: a host array of phases (d, N), a pair (u_re, u_im) of unit phasors, or the dict
+    `band_phase` returns; three-dimensional phasors (nz, nsel, R) are read at kept time `at` and rows `sites` (default: all) -- host
+    arrays are sliced here, the resident views of band_phase(..., resident=True) are gathered on the device and never cross PCIe.
+    Replicate 0 is always the unit-weight fit; nboot > 0 appends `np.random.default_rng(seed).multinomial(N, [1/N]*N, size=nboot)` as
+    bootstrap weights, or explicit `weights` (B', N) may be given instead.  Returns a dict: `pairs` (P, 2) in the order of
+    np.triu_indices(d, 1), `phi` (P, 2), `cond_coupling` (P,) = I1(k) / I0(k) with k = |phi[p]| (the partial phase-locking value),
+    `chi2` and `pvals` (P,) (the edge test, chi-square with two degrees of freedom; None with inference=False), and with replicates
+    `phi_boot` (B', P, 2), `cond_coupling_boot` (B', P), `status_boot` (B',).  One weighted Gram accumulation on fp64 MFMA and one dense
+    Cholesky solve of order d (d - 1) per replicate; the same call gives the same bits.  np.linalg.LinAlgError if the unit-weight
+    fit is singular; a singular replicate stays NaN (one warning).  No counterpart in the package: the reference's scripts call
+    pyTG's torusGraphs(X, selMode=(False, True, False)) in a bootstrap loop (auditory_lfp/torus_graph_fit.py,
+    neuropixels/fit_torus_graph.py)."""
+    if isinstance(phases_or_phasors, dict):
+        u_re, u_im = phases_or_phasors["u_re"], phases_or_phasors["u_im"]
+    elif isinstance(phases_or_phasors, (tuple, list)):
+        u_re, u_im = phases_or_phasors
+    else:
+        ph = np.asarray(phases_or_phasors, dtype=np.float64)
+        u_re, u_im = np.cos(ph), np.sin(ph)
+    shape = tuple(int(v) for v in u_re.shape)
+    if len(shape) not in (2, 3) or tuple(u_im.shape) != shape:
+        raise ValueError("the phases / phasors must be (d, N), or (nz, nsel, R) read at one kept time")
+    N = shape[-1]
+    if isinstance(u_re, _hip.DeviceArray) or isinstance(u_im, _hip.DeviceArray):
+        if getattr(u_re, "name", None) != "phasor_re" or getattr(u_im, "name", None) != "phasor_im" or len(shape) != 3:
+            raise ValueError("device phasors must be the views band_phase(..., resident=True) returned, (nz, nsel, R)")
+        sites = np.arange(shape[0]) if sites is None else np.asarray(sites, dtype=np.intp).reshape(-1)
+        w = _torus_graph_weights(N, weights, nboot, seed)
+        res = u_re._owner.torus_graph_resident(sites, at, shape, weights=w, inference=inference)
+        return _torus_graph_result(res, sites.size, inference)
+    u_re, u_im = np.asarray(u_re, dtype=np.float64), np.asarray(u_im, dtype=np.float64)
+    if len(shape) == 3:
+        u_re, u_im = u_re[:, at, :], u_im[:, at, :]
+    if sites is not None:
+        sel = np.asarray(sites, dtype=np.intp).reshape(-1)
+        u_re, u_im = u_re[sel], u_im[sel]
+    w = _torus_graph_weights(N, weights, nboot, seed)
+    res = (ctx or _hip.default_context()).torus_graph(u_re, u_im, weights=w, inference=inference)
+    return _torus_graph_result(res, u_re.shape[0], inference)
 
 
 def fit_trial_shifts(evec_s, evec_t, Dvec, lfp_trials, mu_lfp, t, tau0=None, mutau=0.0, sigtau=10.0, width=None,

@@ -417,6 +417,37 @@ int gpcsd_plv(gpcsd_ctx *ctx, const double *u_re, const double *u_im, int nz, in
  * (S * nsel * nz * nz doubles each).  Waits for its own work and leaves every other buffer alone.  rc -4 unless the last
  * gpcsd_analytic_resident call stored both halves of the phasors with nz, nsel and M = R * S as given here. */
 int gpcsd_plv_resident(gpcsd_ctx *ctx, int nz, int nsel, int R, int S);
+/* Solve L^T X = B with the lower Cholesky factor L (n, n): the transposed companion of gpcsd_trsm_lower, same inverted-diagonal-block
+ * + GEMM scheme, host arrays, B and X (n, nrhs); L is not modified.  No reference counterpart in the package; it serves
+ * gpcsd_torus_graph (auditory_lfp/torus_graph_fit.py, neuropixels/fit_torus_graph.py: phi = L^-T L^-1 H). */
+int gpcsd_trsm_lower_trans(gpcsd_ctx *ctx, const double *L, int n, const double *B, int nrhs, double *X);
+/* Phase-difference torus graph by score matching, for B weighted replicates of the trials (bootstrap resamples as multiplicity
+ * vectors).  No reference counterpart in the package; usage note: it replaces the torusGraphs(X, selMode=(False, True, False)) fit and
+ * the bootstrap loop around it that the reference's analyses end with (auditory_lfp/torus_graph_fit.py,
+ * neuropixels/fit_torus_graph.py), which call a package that is not part of the reference.  Unit phasors u = u_re + i u_im (d, N) of d
+ * nodes over N trials; pairs p = (i, j), i < j, in the order of np.triu_indices(d, 1), P = d (d - 1) / 2, m = 2 P.  Per trial
+ * c_p = cos(x_i - x_j) = re_i re_j + im_i im_j, s_p = sin(x_i - x_j) = im_i re_j - re_i im_j, S = (c_0, s_0, c_1, s_1, ...), and the
+ * m x d Jacobian D with D[2p][i] = -s_p, D[2p][j] = s_p, D[2p+1][i] = c_p, D[2p+1][j] = -c_p.  With weights w[b][n] >= 0 (B, N) and
+ * W_b their row sums (weights == NULL with B == 1: all ones),
+ *   Gamma_b = 1/W_b sum_n w[b][n] D_n D_n^T,   H_b = 2/W_b sum_n w[b][n] S_n,   phi_b = Gamma_b^-1 H_b        (dense Cholesky, fp64 MFMA)
+ * and for replicate 0 only  r_n = D_n (D_n^T phi_0) - 2 S_n,  Sigma = Gamma_0^-1 (1/W_0 sum_n w[0][n] r_n r_n^T) Gamma_0^-1 / W_0,
+ * chi2[p] = phi_p^T (Sigma_pp)^-1 phi_p with the 2 x 2 diagonal block of Sigma (the p-value is exp(-chi2 / 2)).
+ * Outputs: phi (B, P, 2); status (B): 0, or 1 + the failing pivot of that replicate's factorisation (a pivot of rounding size counts
+ * as failing) -- that replicate's phi is NaN, the others are unaffected; optional (NULL skips the work) and of replicate 0: chi2 (P),
+ * gamma0 (m, m) symmetric bit for bit with exact zeros between pairs that share no node, h0 (m).  Fixed summation order, no atomics:
+ * the same call returns the same bits, however the replicates are chunked (GPCSD_TORUS_CHUNK_MB megabytes of Gamma and node blocks
+ * per chunk, default 256, read per call).  rc 0 when the work ran (failures are in status); rc -3: NULL arguments or B < 1; rc -22:
+ * d < 2, N < 1, a negative or non-finite weight, a zero row sum; GPCSD_ERR_CAPACITY: d > 128 (or N >= 2^22), before anything is read. */
+int gpcsd_torus_graph(gpcsd_ctx *ctx, const double *u_re, const double *u_im, int d, int N, const double *weights, int B,
+                      double *phi, int *status, double *chi2, double *gamma0, double *h0);
+/* Same computation (no reference counterpart in the package; usage note as gpcsd_torus_graph: auditory_lfp/torus_graph_fit.py,
+ * neuropixels/fit_torus_graph.py) on the unit phasors gpcsd_analytic_resident left in "phasor_re" / "phasor_im", read as
+ * (nz, nsel, R): the nodes are the rows sites[0..d) at kept time j, gathered on the device, the R trials are N.  The results are small
+ * and come back to the host; every named device buffer of other calls is left alone.  rc -4 unless the last gpcsd_analytic_resident
+ * call stored both halves of the phasors with nz, nsel and M = R as given here (posterior draws, S > 1, and trial-sharded contexts
+ * are out of scope: fetch the phasors and use gpcsd_torus_graph); rc -3 also for j or a site out of range. */
+int gpcsd_torus_graph_resident(gpcsd_ctx *ctx, const int *sites, int d, int j, int nz, int nsel, int R, const double *weights, int B,
+                               double *phi, int *status, double *chi2);
 /* copy `count` doubles of the named ctx-owned device buffer to host; rc -2 if the name is unknown; rc > 0 if the
  * asynchronous gpcsd_predict_resident that produced the buffer failed numerically */
 int gpcsd_fetch(gpcsd_ctx *ctx, const char *name, double *host, long count);
