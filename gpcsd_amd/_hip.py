@@ -19,6 +19,7 @@ KIND_SE, KIND_MATERN, KIND_HOST = 0, 1, 2
 ERR_CAPACITY = -7
 MAX_EIG_N = 4096                 # GPCSD_MAX_EIG_N: rows of one eigenproblem (after symmetry folding)
 MAX_GEMM_LD_KMAJOR = 1 << 23     # GPCSD_MAX_GEMM_LD_KMAJOR: ntrials * nt of one resident block of trials
+MAX_MISSING = 8192               # GPCSD_MAX_MISSING: missing samples of one trial in the masked calls
 PRED_CSD, PRED_LFP, PRED_BOTH = 1, 2, 3
 
 _c_double_p = ctypes.POINTER(ctypes.c_double)
@@ -183,6 +184,10 @@ SIGNATURES = {
     "gpcsd_sample_prior": (_I, [_P, ctypes.POINTER(HParams), _I, _DP, _I, _DP]),
     "gpcsd_normals": (_I, [_P, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_ulonglong, _L, _DP]),
     "gpcsd_set_trial_offset": (_I, [_P, _L]),
+    "gpcsd_predict_masked": (_I, [_P, ctypes.POINTER(HParams), _P, _I, _DP, _I, _DP, _I, _I, _DP, _DP, _DP, _DP]),
+    "gpcsd_predict_masked_resident": (_I, [_P, ctypes.POINTER(HParams), _P, _I, _DP, _I, _DP, _I, _I, _I]),
+    "gpcsd_loglik_masked": (_I, [_P, ctypes.POINTER(HParams), _P, _I, _DP, _DP, ctypes.POINTER(ctypes.c_long)]),
+    "gpcsd_masked_gram": (_I, [_P, _DP, _I, _DP, _I, _DP, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _I, _DP]),
     "gpcsd_sample_posterior": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _I, ctypes.c_ulonglong, _DP, _DP, _DP, _DP]),
     "gpcsd_sample_posterior_resident": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _I, ctypes.c_ulonglong, _DP, _DP]),
     "gpcsd_set_gram_precision": (_I, [_P, _I]),
@@ -975,6 +980,66 @@ class Context:
         self._check(self._lib.gpcsd_loo_contract(self._h, _ptr(V), _ptr(Qt), _ptr(c), _ptr(Y), nx, int(R), nt, K, _ptr(mean), _ptr(lpd),
                                                  _ptr(sse)))
         return mean, lpd, sse
+
+    # ---- missing samples (masked.hip, capi_masked.inl) ----
+    @staticmethod
+    def _mask_bytes(mask):
+        """(bytes (nx, nt, mask_trials) C order, mask_trials) of a boolean mask (nx, nt) or (nx, nt, ntrials); True = observed."""
+        mask = np.asarray(mask)
+        if mask.ndim == 2:
+            mask = mask[:, :, None]
+        m8 = np.ascontiguousarray(mask != 0, dtype=np.uint8)
+        return m8, m8.shape[2]
+
+    def predict_masked(self, hp, mask, z, tstar, type_code, shape, want_lists=True):
+        """gpcsd_predict_masked: as predict(at=True) on the observed samples only.  shape = (nz, ntstar, ntrials)."""
+        z = _arr(z)
+        tstar = _arr(tstar).reshape(-1)
+        m8, mt = self._mask_bytes(mask)
+        nz, ntstar, R = shape
+        C = hp.n_temporal
+        bufs = {}
+        for name, bit in (("csd", PRED_CSD), ("lfp", PRED_LFP)):
+            on = bool(type_code & bit)
+            bufs[name] = pinned_pool.empty((nz, ntstar, R)) if on else None
+            bufs[name + "_list"] = pinned_pool.empty((C, nz, ntstar, R)) if on and want_lists else None
+        self._check(self._lib.gpcsd_predict_masked(self._h, ctypes.byref(hp), m8.ctypes.data_as(_P), mt, _ptr(z), nz, _ptr(tstar),
+                                                   tstar.size, int(type_code), _ptr(bufs["csd_list"]), _ptr(bufs["csd"]),
+                                                   _ptr(bufs["lfp_list"]), _ptr(bufs["lfp"])))
+        return {k: v for k, v in bufs.items() if v is not None}
+
+    def predict_masked_resident(self, hp, mask, z, tstar, type_code, want_lists=True):
+        """The same into the device buffers of predict_resident only; read back with fetch()."""
+        z = _arr(z)
+        tstar = _arr(tstar).reshape(-1)
+        m8, mt = self._mask_bytes(mask)
+        self._check(self._lib.gpcsd_predict_masked_resident(self._h, ctypes.byref(hp), m8.ctypes.data_as(_P), mt, _ptr(z), z.shape[0],
+                                                            _ptr(tstar), tstar.size, int(type_code), int(bool(want_lists))))
+
+    def loglik_masked(self, hp, mask, ntrials):
+        """gpcsd_loglik_masked: ((sum log det A_OO, sum of the quadratic forms), per-trial rows (ntrials, 2), n_obs)."""
+        m8, mt = self._mask_bytes(mask)
+        out = np.empty(2)
+        rows = np.empty((int(ntrials), 2))
+        n_obs = ctypes.c_long(0)
+        self._check(self._lib.gpcsd_loglik_masked(self._h, ctypes.byref(hp), m8.ctypes.data_as(_P), mt, _ptr(out), _ptr(rows),
+                                                  ctypes.byref(n_obs)))
+        return (float(out[0]), float(out[1])), rows, int(n_obs.value)
+
+    def masked_gram(self, Qs, Qt, D, xi, ti):
+        """The Schur complement's assembly alone (gpcsd_masked_gram): Qs (nx, nx), Qt (nt, nt), D (nx, nt) > 0, samples (xi[p], ti[p])
+        -> G (m, m) = Phi diag(1 / D) Phi^T, Phi[p] = Qs[xi[p]] (x) Qt[ti[p]]."""
+        Qs, Qt, D = _arr(Qs), _arr(Qt), _arr(D)
+        xi = np.ascontiguousarray(xi, dtype=np.int32).reshape(-1)
+        ti = np.ascontiguousarray(ti, dtype=np.int32).reshape(-1)
+        nx, nt, m = Qs.shape[0], Qt.shape[0], xi.size
+        if Qs.shape != (nx, nx) or Qt.shape != (nt, nt) or D.shape != (nx, nt) or ti.size != m:
+            raise ValueError("masked_gram: Qs (nx, nx), Qt (nt, nt), D (nx, nt), xi and ti of one length")
+        G = np.empty((m, m))
+        ip = ctypes.POINTER(ctypes.c_int)
+        self._check(self._lib.gpcsd_masked_gram(self._h, _ptr(Qs), nx, _ptr(Qt), nt, _ptr(D), xi.ctypes.data_as(ip), ti.ctypes.data_as(ip),
+                                                m, _ptr(G)))
+        return G
 
     # ---- band phase and phase locking (phase.hip) ----
     ANALYTIC_OUTPUTS = (("phase", "phase_out"), ("amp", "phase_amp"), ("u_re", "phasor_re"), ("u_im", "phasor_im"))

@@ -195,6 +195,39 @@ void k_tg_residuals(gpcsd_ctx *c, const TgDesc &t, const double *phi, double *g,
 // chi2[p] = phi_p^T Sigma_pp^-1 phi_p with Sigma_pp = 1/W^2 sum_n w_n z_n z_n^T over rows 2p, 2p + 1 of Z (m x N)
 void k_tg_chi2(gpcsd_ctx *c, const double *Z, const double *w, const double *phi, int P, int N, double W, double *chi2, hipStream_t s);
 
+// ---------------------------------------------------------------- missing samples (masked.hip)
+// The grouped, K-scaled symmetric product G = (A^-1)_MM of m missing samples sorted by time, then electrode, cut into strips of up
+// to MASKED_STRIP samples of one time group; a tile is MASKED_TILE_STRIPS x MASKED_TILE_STRIPS strips.  One launch covers the tile
+// rows [t0, t1) and every tile column on or below the diagonal:
+//   G[p][q] = sum_a Qs[xi[p]][a] Qs[xi[q]][a] H[a][grp(p) - gA][grp(q)],   p >= q, and its mirror image from the same register.
+constexpr int MASKED_STRIP = 16, MASKED_TILE_STRIPS = 4;
+struct MaskedGramDesc {
+    const double *Qs = nullptr;     // (nx, nx) row-major
+    int nx = 0;
+    const int *xi = nullptr;        // [m] electrode of sample p
+    const int *s_off = nullptr, *s_cnt = nullptr, *s_grp = nullptr;      // strips, padded with empty ones to a multiple of 4
+    const double *H = nullptr;      // [a][g - gA][g'], g' < ldh
+    long sH = 0, ldh = 0;
+    int gA = 0;
+    int t0 = 0, t1 = 0;
+    int m = 0;
+    double *G = nullptr;            // (m, m)
+};
+void k_masked_gram(gpcsd_ctx *c, const MaskedGramDesc &d, hipStream_t s);
+void k_gather_rows(gpcsd_ctx *c, const double *Q, int n, const int *rows, int nr, double *out, hipStream_t s);     // out[j] = Q[rows[j]]
+// out[x][r][t] = mask[x][t][r] ? y[x][r][t] : 0 (a selection); mask (nx, nt, MT) bytes, MT == 1: one mask for all R trials
+void k_mask_fill(gpcsd_ctx *c, const double *y, const unsigned char *mask, int MT, int nx, int R, int nt, double *out, hipStream_t s);
+// out[r] = sum over the observed samples of trial r of y V (both [x][r][t]), in a fixed order
+void k_mask_dot(gpcsd_ctx *c, const double *y, const double *V, const unsigned char *mask, int MT, int nx, int R, int nt, double *out,
+                hipStream_t s);
+// C[p][k] = V[xi[p]][trial[k]][ti[p]]  and  U[xi[p]][slot[k]][ti[p]] = -X[p][k] (U of na slots), p < m, k < nr
+void k_mask_gather(gpcsd_ctx *c, const double *V, const int *xi, const int *ti, int m, const int *trial, int nr, int R, int nt, double *C,
+                   hipStream_t s);
+void k_mask_scatter(gpcsd_ctx *c, const double *X, const int *xi, const int *ti, int m, const int *slot, int nr, int na, int nt, double *U,
+                    hipStream_t s);
+void k_mask_colsumsq(gpcsd_ctx *c, const double *Z, int m, int nr, const int *trial, double *out, hipStream_t s);   // out[trial[k]] = |Z[:, k]|^2
+void k_mask_add(gpcsd_ctx *c, double *B, const double *B2, const int *trial, int nx, int R, int na, int nt, hipStream_t s);
+
 // ---------------------------------------------------------------- batched hyper-parameter sets
 // Device image of gpcsd_hparams for batched evaluations (gpcsd_loglik_grad_batch): one entry per hyper-parameter set.  The
 // Gram builders / derivative kernels take an optional table: with `tab` they run once for all B sets (the set index is a grid

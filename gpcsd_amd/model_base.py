@@ -774,6 +774,64 @@ class GPCSDModel:
                 res = {k: sh.gather_trials(v) for k, v in res.items()}
         self._store_predictions(res, z, tstar)
 
+    def _masked_args(self, mask, who):
+        if getattr(self, "_sharding", None) is not None:
+            raise NotImplementedError(who + ": trial-sharded models are not supported")
+        if self._uses_host_kt():
+            raise NotImplementedError(who + ": user-defined temporal covariances are not supported; only GPCSDTemporalCovSE / "
+                                      "GPCSDTemporalCovMatern components are")
+        mask = np.asarray(mask)
+        shape = tuple(np.shape(self.lfp))
+        if len(shape) != 3 or mask.shape not in (shape, shape[:2]):
+            raise ValueError("%s: mask must have shape (nx, nt, ntrials) = %s or (nx, nt), not %s" % (who, shape, mask.shape))
+        return mask
+
+    def predict_masked(self, z, tstar, mask, type="csd", resident=False):
+        """`predict_at(z, tstar)` when samples of the recording are MISSING: the posterior mean given the observed samples only.
+        `mask` is a boolean array (nx, nt, ntrials), or (nx, nt) for one mask shared by all trials; True means observed.  Stores
+        and returns what `predict_at` does (`csd_pred`, `lfp_pred`, the `*_list` attributes, `t_pred`, `x_pred`; `resident` as there).
+
+        Exact and without iteration: with A the covariance of a full trial (no jitter, as in `predict`), M a trial's m missing
+        samples and y~ the trial with zeros there, the weights are A^-1 (y~ + E_M u) with u = -G^-1 (A^-1 y~)_M and G = (A^-1)_MM, a
+        dense m x m matrix per distinct mask that is assembled from the eigen-decomposition the full-grid calls use and factored by
+        Cholesky.  The values of `lfp` at masked-out samples are never read as numbers: NaN or Inf there change no bit.  A trial
+        without an observed sample predicts 0.  More than 8192 missing samples in one trial (GPCSD_MAX_MISSING) raise
+        GPCSDCapacityError.  ValueError on a mask of another shape; NotImplementedError on trial-sharded models and on user-defined
+        temporal covariances.  No reference counterpart."""
+        if type not in ("csd", "lfp", "both"):
+            raise ValueError("type must be 'csd', 'lfp' or 'both'")
+        mask = self._masked_args(mask, "predict_masked")
+        ctx = self._sync_device()
+        z = np.asarray(z, dtype=np.float64)
+        z2 = z.reshape(-1, 1) if self.dim == 1 else z
+        tstar = np.asarray(tstar)
+        if tstar.size < 1:
+            raise ValueError("tstar must hold at least one time")
+        hp, _keep = self._hparams(0.0)                     # no jitter, as predict
+        code = {"csd": _hip.PRED_CSD, "lfp": _hip.PRED_LFP, "both": _hip.PRED_BOTH}[type]
+        R = np.shape(self.lfp)[2]
+        if resident:
+            ctx.predict_masked_resident(hp, mask, z2, tstar, code, want_lists=True)
+            res = self._device_predictions(ctx, code, z2.shape[0], tstar.size, R)
+        else:
+            res = ctx.predict_masked(hp, mask, z2, tstar, code, (z2.shape[0], tstar.size, R))
+        self._store_predictions(res, z, tstar)
+        return res
+
+    def loglik_masked(self, mask):
+        """Log marginal likelihood of the OBSERVED samples (`mask` as in `predict_masked`) under the model of the masked predictions
+        (no jitter), in `loglik()`'s convention without the 2 pi term: -1/2 sum_r log det A_OO - 1/2 sum_r y_O^T A_OO^-1 y_O.  Sets
+        `loglik_masked_trials` ((ntrials, 2): the two terms of every trial before the factor -1/2; a trial without an observed sample
+        has (0, 0)) and `n_obs`, the number of observed samples, so that a caller comparing masks can add -1/2 n_obs log(2 pi).
+        Exact (the Schur complement of the missing set); errors as `predict_masked`.  No reference counterpart."""
+        mask = self._masked_args(mask, "loglik_masked")
+        ctx = self._sync_device()
+        hp, _keep = self._hparams(0.0)
+        (ld, qd), rows, n_obs = ctx.loglik_masked(hp, mask, np.shape(self.lfp)[2])
+        self.loglik_masked_trials = rows
+        self.n_obs = n_obs
+        return np.float64(-0.5 * ld - 0.5 * qd)
+
     _VAR_BUFFERS = (("csd", _hip.PRED_CSD, "pred_var_csd"), ("lfp", _hip.PRED_LFP, "pred_var_lfp"))
 
     def predict_var(self, z, tstar, type="csd", resident=False):

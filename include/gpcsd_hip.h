@@ -48,6 +48,9 @@ extern "C" {
  *                           electrodes; shard trials over ranks beyond that)                                          */
 #define GPCSD_MAX_EIG_N           4096
 #define GPCSD_MAX_GEMM_LD_KMAJOR  (1L << 23)
+/*   GPCSD_MAX_MISSING         missing samples of ONE trial in gpcsd_predict_masked / gpcsd_loglik_masked (m of gpcsd_masked_gram):
+ *                           the Schur complement of the missing set is a dense m x m matrix, 512 MB of fp64 at the limit       */
+#define GPCSD_MAX_MISSING         8192
 #define GPCSD_ERR_CAPACITY      (-7)
 
 #define GPCSD_PRED_CSD  1
@@ -507,6 +510,43 @@ int gpcsd_sample_posterior(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double
 int gpcsd_sample_posterior_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double *z, int nz,
                                     const double *tstar, int ntstar, int type, int nsamples, unsigned long long seed,
                                     const double *normals_xi, const double *normals_eps);
+
+/* Posterior means with MISSING SAMPLES: gpcsd_predict_at of the model conditioned on the observed samples only.  NO REFERENCE
+ * COUNTERPART: the reference needs the full (electrode, time, trial) grid.  mask: bytes in the data's layout (nx, nt, mask_trials),
+ * C order, non-zero = observed; mask_trials == ntrials, or 1 for one (nx, nt) mask shared by all trials.  Exact, no iteration: with
+ * A = Ks (x) Kt + sig2n I of a full trial (no jitter; a noise list on the eigen-index), M the m missing samples of a trial, y~ the
+ * trial with zeros on M, c = (A^-1 y~)_M and G = (A^-1)_MM (dense, SPD, one per DISTINCT mask),
+ *   A_OO^-1 y_O = [A^-1 (y~ + E_M u)]_O,  u = -G^-1 c,
+ * i.e. the full-grid solve of gpcsd_predict_at on the data with u imputed.  The zeros are a SELECTION: a masked-out value is never an
+ * arithmetic operand, NaN / Inf there change no bit of any output.  A trial without an observed sample predicts 0.  The same call
+ * returns the same bits.  G is assembled in chunks whose scratch fits GPCSD_MASKED_SCRATCH_MB megabytes (default 256; read per call).
+ * z, tstar, `type`, outputs and their layouts as gpcsd_predict_at.  rc -3: bad arguments, mask_trials not in {1, ntrials}, a
+ * user-defined temporal covariance (GPCSD_KIND_HOST); GPCSD_ERR_CAPACITY, before any data is read: a trial with more than
+ * GPCSD_MAX_MISSING missing samples (unless none is observed), or gpcsd_predict_at's limits; rc > 0: numerical failure, a G that is
+ * not positive definite included; rc -4 without resident data. */
+int gpcsd_predict_masked(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const unsigned char *mask, int mask_trials,
+                         const double *z, int nz, const double *tstar, int ntstar, int type,
+                         double *csd_list, double *csd, double *lfp_list, double *lfp);
+/* Same computation (no reference counterpart), results left in the named device buffers of gpcsd_predict_at_resident.  Waits for its
+ * own work: a numerical failure (rc > 0) is returned by the call itself. */
+int gpcsd_predict_masked_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const unsigned char *mask, int mask_trials,
+                                  const double *z, int nz, const double *tstar, int ntstar, int type, int want_lists);
+/* Log-likelihood of the OBSERVED samples under the model of gpcsd_predict_masked (no jitter).  NO REFERENCE COUNTERPART.  mask and
+ * mask_trials as gpcsd_predict_masked.  out2 = {sum_r (log det A + log det G_r), sum_r (y~_r^T A^-1 y~_r - c_r^T G_r^-1 c_r)} =
+ * {sum_r log det A_OO, sum_r y_O^T A_OO^-1 y_O}; the value is -1/2 out2[0] - 1/2 out2[1], loglik()'s convention without a 2 pi
+ * term -- *n_obs (may be NULL) receives the number of observed samples over all trials so that a caller comparing masks can add
+ * -1/2 n_obs log(2 pi).  per_trial (ntrials, 2), C order, may be NULL: the two terms of every trial; a trial without an observed
+ * sample contributes (0, 0).  Fixed summation orders: the same call returns the same bits.  Return codes as gpcsd_predict_masked. */
+int gpcsd_loglik_masked(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const unsigned char *mask, int mask_trials, double *out2,
+                        double *per_trial, long *n_obs);
+/* The Schur complement's assembly alone, on host arrays (no reference counterpart; masked.hip): Qs (nx, nx) and Qt (nt, nt), C order,
+ * eigen-index in columns; D (nx, nt) > 0; samples (xi[p], ti[p]), p < m, in any order.  G (m, m), C order, in the caller's order:
+ *   G[p][q] = sum_{a,b} Qs[xi[p]][a] Qs[xi[q]][a] Qt[ti[p]][b] Qt[ti[q]][b] / D[a][b]
+ * as sum_a Qs[xi[p]][a] Qs[xi[q]][a] H_a[j(p)][j(q)], H_a = Qt_u diag(1 / D[a, :]) Qt_u^T over the distinct times.  Symmetric bit for
+ * bit; the same call returns the same bits.  rc -3: NULL or empty arguments, a sample outside the grid; GPCSD_ERR_CAPACITY (before
+ * anything is read): m > GPCSD_MAX_MISSING. */
+int gpcsd_masked_gram(gpcsd_ctx *ctx, const double *Qs, int nx, const double *Qt, int nt, const double *D,
+                      const int *xi, const int *ti, int m, double *G);
 
 /* Per-trial whitened quadratic forms  out[b] = sum( (Qs^T resid_b Qt)^2 / Dvec )  for nb residual matrices at once, given a
  * cached decomposition (Qs, Qt, Dvec) from gpcsd_eig_D.  resid is (nx, nt, nb) C-order like lfp.  This is the projection
