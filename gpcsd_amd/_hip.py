@@ -176,6 +176,10 @@ SIGNATURES = {
     "gpcsd_analytic_resident": (_I, [_P, ctypes.c_char_p, _L, _I, _I, _L, _DP, _DP, _I, _I]),
     "gpcsd_plv": (_I, [_P, _DP, _DP, _I, _I, _I, _I, _DP, _DP, _DP]),
     "gpcsd_plv_resident": (_I, [_P, _I, _I, _I, _I]),
+    "gpcsd_power_spectrum": (_I, [_P, _DP, _I, _I, _I, _I, _DP, _DP, _I, _DP, _DP, _DP, _DP]),
+    "gpcsd_power_spectrum_resident": (_I, [_P, ctypes.c_char_p, _L, _I, _I, _I, _I, _DP, _DP, _I, _I]),
+    "gpcsd_cross_spectrum": (_I, [_P, _DP, _DP, _I, _I, _I, _I, _DP, _DP, _DP]),
+    "gpcsd_cross_spectrum_resident": (_I, [_P, _I, _I, _I, _I]),
     "gpcsd_trsm_lower_trans": (_I, [_P, _DP, _I, _DP, _I, _DP]),
     "gpcsd_torus_graph": (_I, [_P, _DP, _DP, _I, _I, _DP, _I, _DP, ctypes.POINTER(_I), _DP, _DP, _DP]),
     "gpcsd_torus_graph_resident": (_I, [_P, ctypes.POINTER(_I), _I, _I, _I, _I, _I, _DP, _I, _DP, ctypes.POINTER(_I), _DP]),
@@ -1102,6 +1106,67 @@ class Context:
         (c_re, c_im, plv) of "plv_re", "plv_im", "plv_abs", each (S, nsel, nz, nz)."""
         self._check(self._lib.gpcsd_plv_resident(self._h, int(nz), int(nsel), int(R), int(S)))
         return tuple(self.device_array(b, (int(S), int(nsel), int(nz), int(nz))) for b in ("plv_re", "plv_im", "plv_abs"))
+
+    # ---- power spectrum, cross-spectrum and coherence (spectrum.hip) ----
+    SPECTRUM_OUTPUTS = (("power", "spec_power"), ("re", "spec_re"), ("im", "spec_im"))
+
+    @classmethod
+    def _spectrum_mask(cls, want):
+        names = [k for k, _ in cls.SPECTRUM_OUTPUTS]
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if any(w not in names for w in want):
+            raise ValueError("want may name %s" % (names,))
+        return sum(1 << names.index(w) for w in set(want))
+
+    def power_spectrum(self, x, A, want=()):
+        """Trial-averaged power of the host array x (nz, nts, R, S) under the spectral operator A (nrow, nts) (gpcsd_power_spectrum):
+        dict with "psd" (nz, nrow, S) and the wanted ones of "power", "re", "im", each (nz, nrow, R, S); the others are not stored."""
+        x = _arr(x)
+        if x.ndim != 4:
+            raise ValueError("power_spectrum: x must be (nz, nts, R, S)")
+        nz, nts, R, S = x.shape
+        Are, Aim = self._operator_parts(A, nts)
+        mask = self._spectrum_mask(want)
+        nrow = Are.shape[0]
+        out = {k: pinned_pool.empty((nz, nrow, R, S)) if mask & (1 << i) else None for i, (k, _) in enumerate(self.SPECTRUM_OUTPUTS)}
+        psd = np.empty((nz, nrow, S))
+        self._check(self._lib.gpcsd_power_spectrum(self._h, _ptr(x), nz, nts, R, S, _ptr(Are), _ptr(Aim), nrow, _ptr(psd), _ptr(out["power"]),
+                                                   _ptr(out["re"]), _ptr(out["im"])))
+        res = {"psd": psd}
+        res.update((k, v) for k, v in out.items() if v is not None)
+        return res
+
+    def power_spectrum_resident(self, src_name, src_offset, shape, A, want=()):
+        """The same on the named device buffer `src_name` from `src_offset` doubles on, read as shape = (nz, nts, R, S)
+        (gpcsd_power_spectrum_resident); "psd" and the wanted outputs stay in "spec_psd", "spec_power", "spec_re", "spec_im" --
+        returned as zero-copy views.  The phase, PLV and prediction buffers are left alone."""
+        nz, nts, R, S = (int(v) for v in shape)
+        Are, Aim = self._operator_parts(A, nts)
+        mask = self._spectrum_mask(want)
+        nrow = Are.shape[0]
+        self._check(self._lib.gpcsd_power_spectrum_resident(self._h, src_name.encode(), int(src_offset), nz, nts, R, S, _ptr(Are), _ptr(Aim),
+                                                            nrow, mask))
+        res = {"psd": self.device_array("spec_psd", (nz, nrow, S))}
+        res.update((k, self.device_array(buf, (nz, nrow, R, S))) for i, (k, buf) in enumerate(self.SPECTRUM_OUTPUTS) if mask & (1 << i))
+        return res
+
+    def cross_spectrum(self, X_re, X_im, want_coh=True):
+        """Cross-spectral matrix of all site pairs from host coefficients (nz, nrow, R, S) (gpcsd_cross_spectrum): (s_re, s_im, coh),
+        each (S, nrow, nz, nz), s_re + i s_im = mean over the trials of X_a conj(X_b); want_coh=False skips the coherence (None)."""
+        X_re, X_im = _arr(X_re), _arr(X_im)
+        if X_re.ndim != 4 or X_re.shape != X_im.shape:
+            raise ValueError("cross_spectrum: X_re and X_im must both be (nz, nrow, R, S)")
+        nz, nrow, R, S = X_re.shape
+        s_re, s_im = np.empty((S, nrow, nz, nz)), np.empty((S, nrow, nz, nz))
+        coh = np.empty((S, nrow, nz, nz)) if want_coh else None
+        self._check(self._lib.gpcsd_cross_spectrum(self._h, _ptr(X_re), _ptr(X_im), nz, nrow, R, S, _ptr(s_re), _ptr(s_im), _ptr(coh)))
+        return s_re, s_im, coh
+
+    def cross_spectrum_resident(self, nz, nrow, R, S=1):
+        """The same on the coefficients power_spectrum_resident left in "spec_re" / "spec_im" (gpcsd_cross_spectrum_resident):
+        zero-copy views (s_re, s_im, coh) of "xspec_re", "xspec_im", "xspec_coh", each (S, nrow, nz, nz)."""
+        self._check(self._lib.gpcsd_cross_spectrum_resident(self._h, int(nz), int(nrow), int(R), int(S)))
+        return tuple(self.device_array(b, (int(S), int(nrow), int(nz), int(nz))) for b in ("xspec_re", "xspec_im", "xspec_coh"))
 
     # ---- phase-difference torus graph (torus.hip) ----
     def trsm_lower_trans(self, L, B):

@@ -219,6 +219,9 @@ struct gpcsd_ctx {
     // shape (nz, nsel, M) of the unit phasors the last gpcsd_analytic_resident left in "phasor_re" / "phasor_im" (0: none, or only
     // one of the two): what gpcsd_plv_resident may read
     long phasor_shape[3] = {0, 0, 0};
+    // shape (nz, nrow, R, S) of the coefficients the last gpcsd_power_spectrum_resident left in "spec_re" / "spec_im" (0: none, or
+    // only one of the two): what gpcsd_cross_spectrum_resident may read
+    long spec_shape[4] = {0, 0, 0, 0};
     gpcsd::SymDev sym_s, sym_t;             // reflection symmetry of the electrode / time grids (ns == 0: none found)
     // folded-basis GEMMs (capi.hip): what the electrode symmetry reflects about, host copies of the grids to recognise
     // prediction sites / times with the same symmetry, the symmetry of the last prediction sites, and whether the

@@ -170,6 +170,25 @@ struct PlvDesc {
 };
 void k_plv(gpcsd_ctx *c, const PlvDesc &d, hipStream_t s);
 
+// ---------------------------------------------------------------- power spectrum and coherence (spectrum.hip)
+// Coefficients X[z][j][m] = sum_t (Are + i Aim)[j][t] x[z][t][m] of the field x (nz, nts, R, S) under a spectral operator (nrow, nts),
+// m = r S + s with the draw index innermost, and the power averaged over the trials: psd[z][j][s] = 1/R sum_r |X[z][j][r S + s]|^2,
+// summed in a fixed order through per-tile partial sums (part: nz nrow S power_slots(R S) doubles of scratch), no atomics.  The
+// per-trial outputs power = |X|^2, re, im, each (nz, nrow, R, S), are optional: a null one is not stored.
+struct PowerDesc {
+    const double *X = nullptr;      // (nz, nts, R, S)
+    int nz = 0, nts = 0, R = 0, S = 1;
+    const double *Are = nullptr, *Aim = nullptr;      // (nrow, nts) row-major
+    int nrow = 0;
+    double *part = nullptr, *psd = nullptr;
+    double *power = nullptr, *re = nullptr, *im = nullptr;
+};
+int power_slots(long M);
+void k_power(gpcsd_ctx *c, const PowerDesc &d, hipStream_t s);
+// coh = (sre^2 + sim^2) / (sre[a][a] sre[b][b]) for nmat Hermitian nz x nz matrices in k_plv's layout; 0 where the denominator is 0;
+// symmetric bit for bit when sre is symmetric and sim antisymmetric bit for bit
+void k_coherence(gpcsd_ctx *c, const double *sre, const double *sim, double *coh, int nz, long nmat, hipStream_t s);
+
 // ---------------------------------------------------------------- phase-difference torus graph (torus.hip)
 // d nodes, N trials; node a's phasors are ure / uim [off[a] .. off[a] + N) (off: device table, so a strided slice of the resident
 // phasors and a dense (d, N) upload are one code path); pi / pj: device tables of the P = d (d - 1) / 2 pairs (i < j) in the order

@@ -1003,6 +1003,94 @@ class GPCSDModel:
             setattr(self, name + "_plv", p)
             setattr(self, name + "_plv_angle", np.arctan2(c.imag, c.real))
 
+    def _spectral_source(self, who, name, component):
+        """The field `spectrum()` / `coherence()` work on: the current prediction of type `name`, or one temporal component of it."""
+        x = getattr(self, name + "_pred", None)
+        if x is None:
+            raise RuntimeError("%s: no %s prediction to work on (call predict / predict_at with type=%r first)" % (who, name, name))
+        if component is not None:
+            lst = getattr(self, name + "_pred_list")
+            if not 0 <= int(component) < len(lst):
+                raise ValueError("component must be in [0, %d)" % len(lst))
+            x = lst[int(component)]
+        t = np.asarray(self.t_pred, dtype=np.float64).reshape(-1)
+        if t.size > 2:
+            dt = np.diff(t)
+            if not np.max(np.abs(dt - dt.mean())) <= 1e-6 * abs(dt.mean()):
+                raise ValueError("%s: t_pred is not uniformly spaced; a periodogram needs a uniform grid" % who)
+        return x
+
+    def _spectral_sharding(self, who):
+        sh = getattr(self, "_sharding", None)
+        if sh is not None and getattr(sh, "gather_predictions", False):
+            raise NotImplementedError("%s: gather_predictions does not apply; each rank works on its block of trials" % who)
+        return sh
+
+    def spectrum(self, fs, nfft=None, window="boxcar", scaling="density", detrend=False, rows=None, type="csd", component=None,
+                 per_trial=False, resident=False):
+        """Power spectrum along time of the model's CURRENT prediction, averaged over the trials: what
+        `scipy.signal.periodogram(pred, fs, window, nfft, detrend, scaling=scaling, axis=1)[1].mean(-1)` gives on the host
+        (auditory_lfp/fit_gpcsd_baseline.py:189-195, neuropixels/fit_gpcsd2d.py:120-128), for `csd_pred` / `lfp_pred` or temporal
+        component `component` of their `*_list` forms, host arrays or resident views alike; a resident prediction is read in HBM and
+        only the (nz, nf) result crosses PCIe.  fs is the caller's sampling rate (the time unit of `t_pred` is theirs; `t_pred` must be
+        uniformly spaced: ValueError otherwise); nfft, window, scaling, detrend, rows as in `utility_functions.spectral_operator`
+        (one-sided).  Sets `f_spec` and `csd_psd` / `lfp_psd` (nz, nf); with per_trial=True also `csd_power` / `lfp_power`
+        (nz, nf, ntrials), the periodogram of every trial -- host arrays, or with resident=True (resident predictions, one type per
+        call: the library has one set of result buffers) zero-copy device views.  Under trial sharding the ranks' sums are added (one
+        all-reduce per type) and every rank holds the spectrum over all trials as a host array; the per-trial power stays this rank's
+        block; `gather_predictions` does not apply.  The prediction, phase, variance, leave-one-out and sample attributes are left
+        alone.  No counterpart in the package."""
+        from .utility_functions import power_spectrum, spectral_operator, spectrum_from_sums
+        types = self._types(type)
+        if resident and len(types) > 1:
+            raise ValueError("resident=True holds one field's results: call spectrum() per type")
+        sh = self._spectral_sharding("spectrum")
+        ctx = self._context()
+        for name in types:
+            x = self._spectral_source("spectrum", name, component)
+            if resident and not isinstance(x, _hip.DeviceArray):
+                raise ValueError("resident=True needs a resident prediction")
+            f, A = spectral_operator(x.shape[1], fs, nfft, window, scaling, detrend, True, rows)
+            res = power_spectrum(x, A, per_trial=per_trial, resident=resident, ctx=ctx)
+            psd = res["psd"]
+            if sh is not None:
+                local = psd.numpy() if resident else psd
+                psd = spectrum_from_sums({"psd": sh.allreduce_sum(x.shape[2] * np.asarray(local))}, np.atleast_3d(self.lfp).shape[2])["psd"]
+            setattr(self, name + "_psd", psd)
+            if per_trial:
+                setattr(self, name + "_power", res["power"])
+            self.f_spec = f
+
+    def coherence(self, fs, rows, nfft=None, window="boxcar", scaling="density", detrend=False, type="csd", component=None):
+        """Cross-spectrum and magnitude-squared coherence of all site pairs of the model's CURRENT prediction over the trials, at the
+        frequency indices `rows` of the periodogram `spectrum()` describes (required: the result has len(rows) nz^2 entries).  Sets
+        `csd_xspec` / `lfp_xspec` (nf, nz, nz), complex: xspec[j, a, b] = mean over trials of X_a conj(X_b), which is
+        `scipy.signal.csd(x_b, x_a)` averaged over the trials (SciPy conjugates its first argument; the orientation of `plv()`'s
+        phase_a - phase_b), `csd_coh` / `lfp_coh` = |xspec[a, b]|^2 / (xspec[a, a] xspec[b, b]) -- what `scipy.signal.coherence` gives
+        on the concatenated trials with nperseg = the trial length and no overlap; 0 where a site has no power -- and `f_coh`.  The
+        coherence and xspec.real are symmetric, xspec.imag antisymmetric bit for bit.  `t_pred` must be uniformly spaced.  Under trial
+        sharding each rank forms R_local * xspec of its block, the sums are added over the ranks (one all-reduce per type) and the
+        coherence is formed after the sum; `gather_predictions` does not apply.  The prediction, phase, variance, leave-one-out and
+        sample attributes are left alone.  No counterpart in the package."""
+        from .utility_functions import cross_spectrum, power_spectrum, spectral_operator, spectrum_from_sums
+        if rows is None:
+            raise ValueError("coherence: rows (the frequency indices to keep) is required")
+        types = self._types(type)
+        sh = self._spectral_sharding("coherence")
+        ctx = self._context()
+        for name in types:
+            x = self._spectral_source("coherence", name, component)
+            f, A = spectral_operator(x.shape[1], fs, nfft, window, scaling, detrend, True, rows)
+            res = power_spectrum(x, A, coefficients=True, resident=isinstance(x, _hip.DeviceArray), ctx=ctx)
+            Sx, coh = cross_spectrum(res, ctx=ctx)
+            if sh is not None:
+                sums = sh.allreduce_sum(np.stack([x.shape[2] * Sx.real, x.shape[2] * Sx.imag]))
+                out = spectrum_from_sums({"xspec": sums}, np.atleast_3d(self.lfp).shape[2])
+                Sx, coh = out["xspec"], out["coh"]
+            setattr(self, name + "_xspec", Sx)
+            setattr(self, name + "_coh", coh)
+            self.f_coh = f
+
     def torus_graph(self, type="csd", at=0, sites=None, nboot=0, seed=None):
         """Phase-difference torus graph (score matching) of the phases of the last `phase()` call at kept time `at`, over the trials:
         the CONDITIONAL coupling of every pair of `sites` (default: all prediction sites) given the others, where `plv()` is the

@@ -4,7 +4,9 @@ Mirrors src/gpcsd/utility_functions.py: normalize :7-8, sort_grid :10-13, expand
 :25-33, mykron :35-42 (API parity only -- never on the fast path), comp_eig_D :44-64 (two HIP symmetric
 eigendecompositions + the D vector).  analytic_operator, band_phase, plv, plv_from_sums have no counterpart in the package: they are
 the band-pass + Hilbert + phase-locking step the reference's analysis scripts end with, as one linear operator (host) and two HIP
-launches (csrc/phase.hip); torus_graph, the conditional phase coupling those scripts fit next, likewise (csrc/torus.hip)."""
+launches (csrc/phase.hip); torus_graph, the conditional phase coupling those scripts fit next, likewise (csrc/torus.hip);
+spectral_operator, power_spectrum, cross_spectrum, spectrum_from_sums: the periodogram those scripts take of every prediction, its
+mean over the trials and the coherence of all site pairs (csrc/spectrum.hip)."""
 import numpy as np
 
 from . import _hip
@@ -168,6 +170,161 @@ def plv(phasors_or_phase, resident=False, ctx=None):
         c_re, c_im, p = (v.reshape(out_shape) for v in (ctx or _hip.default_context()).plv(
             np.asarray(u_re, dtype=np.float64).reshape(nz, nsel, R, S), np.asarray(u_im, dtype=np.float64).reshape(nz, nsel, R, S)))
     return p, c_re + 1j * c_im
+
+
+def spectral_operator(n, fs=1.0, nfft=None, window="boxcar", scaling="density", detrend=False, return_onesided=True, rows=None):
+    """(f, A): the complex matrix A (nrow, n), complex128, of a periodogram along a time axis of length n, and its frequencies f:
+    `np.abs(A @ x)**2 == scipy.signal.periodogram(x, fs, window, nfft, detrend, return_onesided, scaling)[1]`.  Every step but the
+    final modulus is linear in the signal for a fixed length, so the operator is their action on the identity along axis 0:
+    rfft(window[:, None] * detrend(I), nfft), each row times the square root of its scale -- 1 / (fs sum w^2) for "density",
+    1 / (sum w)^2 for "spectrum", doubled for the one-sided rows except DC and (nfft even) Nyquist.  window: a name or tuple for
+    `scipy.signal.get_window`, or an array of length n; detrend: False, "constant" or "linear"; nfft < n reads the first nfft samples
+    only, as SciPy does (the window then has that length).  rows: frequency indices to keep, in any order (default: all) -- keeping a
+    frequency is keeping a row.  What the reference's scripts compute per call on the host (auditory_lfp/fit_gpcsd_baseline.py:189-195,
+    neuropixels/fit_gpcsd2d.py:120-128); no counterpart in the package."""
+    import scipy.signal
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be at least 1")
+    if not fs > 0:
+        raise ValueError("fs must be positive")
+    nseg = n
+    if nfft is None:
+        nfft = n
+    else:
+        nfft = int(nfft)
+        if nfft < 1:
+            raise ValueError("nfft must be at least 1")
+        nseg = min(n, nfft)
+    if isinstance(window, (str, tuple)):
+        w = scipy.signal.get_window(window, nseg)
+    else:
+        w = np.asarray(window, dtype=np.float64)
+        if w.ndim != 1 or w.size != nseg:
+            raise ValueError("a window array must have the length of the signal (%d), got %s" % (nseg, w.shape))
+    if detrend is False or detrend is None:
+        T = np.eye(nseg)
+    elif detrend in ("constant", "linear"):
+        T = scipy.signal.detrend(np.eye(nseg), axis=0, type=detrend)
+    else:
+        raise ValueError("detrend must be False, 'constant' or 'linear'")
+    if scaling == "density":
+        scale = 1.0 / (float(fs) * np.sum(w * w))
+    elif scaling == "spectrum":
+        scale = 1.0 / np.sum(w) ** 2
+    else:
+        raise ValueError("scaling must be 'density' or 'spectrum'")
+    T = w[:, None] * T
+    if return_onesided:
+        A = np.fft.rfft(T, nfft, axis=0)
+        f = np.fft.rfftfreq(nfft, 1.0 / float(fs))
+        s = np.full(A.shape[0], scale)
+        s[1:(None if nfft % 2 else -1)] *= 2.0
+    else:
+        A = np.fft.fft(T, nfft, axis=0)
+        f = np.fft.fftfreq(nfft, 1.0 / float(fs))
+        s = np.full(A.shape[0], scale)
+    A = A * np.sqrt(s)[:, None]
+    if nseg < n:
+        A = np.concatenate([A, np.zeros((A.shape[0], n - nseg), dtype=A.dtype)], axis=1)
+    if rows is not None:
+        rows = np.asarray(rows, dtype=np.intp).reshape(-1)
+        A, f = A[rows], f[rows]
+    return np.array(f, dtype=np.float64), np.ascontiguousarray(A, dtype=np.complex128)
+
+
+def power_spectrum(x, A, per_trial=False, coefficients=False, resident=False, ctx=None):
+    """Power spectrum along the time axis of x (nz, n, M) or (nz, n, R, S) -- a NumPy array, or a `_hip.DeviceArray` such as a resident
+    prediction (`m.csd_pred`, `m.csd_pred_list[c]`) or resident posterior draws (R trials, S draws per trial) -- under the operator A
+    (nrow, n) of `spectral_operator`, averaged over the trials: dict with "psd" (nz, nrow), or (nz, nrow, S) for a four-dimensional
+    input (one trial-averaged spectrum per draw: a posterior band for the spectrum); per_trial=True adds "power", |A x|^2 per trial,
+    coefficients=True "re" and "im", the parts of A x that `cross_spectrum` reads, each shaped like x with n -> nrow.  One fp64 MFMA
+    product with the modulus in its epilogue and a sum over the trials in a fixed order (no atomics: the same call gives the same
+    bits, "psd" the same bits whatever else is asked for); outputs not asked for are not stored.  Residency as in `band_phase`: a
+    device input is read where it lies, with resident=True its results are zero-copy views of the library's buffers "spec_psd",
+    "spec_power", "spec_re", "spec_im" (valid until the next call that writes them), otherwise host arrays.  No reference counterpart
+    in the package (its scripts: scipy.signal.periodogram(..., axis=1), then a mean over the trials)."""
+    A = np.asarray(A)
+    shape = tuple(int(v) for v in x.shape)
+    if len(shape) not in (3, 4):
+        raise ValueError("x must be (nz, n, M) or (nz, n, R, S)")
+    nz, n, R = shape[:3]
+    S = shape[3] if len(shape) == 4 else 1
+    want = (("power",) if per_trial else ()) + (("re", "im") if coefficients else ())
+    if A.ndim != 2:
+        raise ValueError("the operator must be (nrow, %d), got %s" % (n, A.shape))
+    out_shape = {k: (nz, A.shape[0]) + shape[2:] for k in want}
+    out_shape["psd"] = (nz, A.shape[0]) + shape[3:]
+    if isinstance(x, _hip.DeviceArray):
+        if x.base is None:
+            raise ValueError("power_spectrum: the device array is not a view of a named buffer of the library")
+        ctx = x._owner
+        res = ctx.power_spectrum_resident(x.base[0], x.base[1], (nz, n, R, S), A, want)
+        if resident:
+            return {k: _hip.DeviceArray(v.ptr, out_shape[k], ctx, v.name) for k, v in res.items()}
+        return {k: ctx.fetch(v.name, out_shape[k]) for k, v in res.items()}
+    if resident:
+        raise ValueError("resident=True needs a device input")
+    res = (ctx or _hip.default_context()).power_spectrum(np.asarray(x, dtype=np.float64).reshape(nz, n, R, S), A, want)
+    return {k: v.reshape(out_shape[k]) for k, v in res.items()}
+
+
+def _coherence(Sx):
+    d = np.real(np.diagonal(Sx, axis1=-2, axis2=-1))
+    den = d[..., :, None] * d[..., None, :]
+    num = Sx.real * Sx.real + Sx.imag * Sx.imag
+    return np.where(den > 0.0, num / np.where(den > 0.0, den, 1.0), 0.0)
+
+
+def spectrum_from_sums(sums, ntrials):
+    """The host-side combine of a trial-sharded job: every rank forms R_local * psd and R_local * Sx of its block of trials, the sums
+    add, and the coherence -- a quotient -- is formed after the sum.  sums: dict with "psd" (the summed R_local * psd) and / or
+    "xspec" (the summed R_local * Sx, complex, or the stacked pair (2, ...) of its parts); returns a dict with "psd" and / or "xspec"
+    (complex) and "coh", over all `ntrials` trials."""
+    out = {}
+    if "psd" in sums:
+        out["psd"] = np.asarray(sums["psd"], dtype=np.float64) / float(ntrials)
+    if "xspec" in sums:
+        s = np.asarray(sums["xspec"])
+        if not np.iscomplexobj(s):
+            s = s[0] + 1j * s[1]
+        out["xspec"] = s / float(ntrials)
+        out["coh"] = _coherence(out["xspec"])
+    return out
+
+
+def cross_spectrum(coeffs, resident=False, ctx=None):
+    """Cross-spectral matrix and magnitude-squared coherence of ALL site pairs over the trials.  Input: the dict `power_spectrum(...,
+    coefficients=True)` returns, or a pair (re, im), each array (nz, nrow, R) or (nz, nrow, R, S).  Returns (Sx, coherence):
+    Sx[j, a, b] = mean over the trials of X_a conj(X_b) at kept frequency j, complex, in the operator's scaling -- that is
+    `scipy.signal.csd(x_b, x_a)` averaged over the trials (SciPy conjugates its FIRST argument), the orientation of `plv`'s
+    phase_a - phase_b -- and coherence[j, a, b] = |Sx[j, a, b]|^2 / (Sx[j, a, a] Sx[j, b, b]), 0 where a site's power is 0; shapes
+    (nrow, nz, nz), or (S, nrow, nz, nz) for a four-dimensional input.  Two launches for all pairs, frequencies and draws; Sx.real and
+    the coherence are symmetric and Sx.imag antisymmetric bit for bit.  Coefficients that are resident views (`power_spectrum(...,
+    coefficients=True, resident=True)`) are read where they lie; resident=True then returns zero-copy views ((s_re, s_im), coherence)
+    of "xspec_re", "xspec_im", "xspec_coh" instead of host arrays.  ctx as in `band_phase`.  No reference counterpart."""
+    re, im = (coeffs["re"], coeffs["im"]) if isinstance(coeffs, dict) else coeffs
+    shape = tuple(int(v) for v in re.shape)
+    if len(shape) not in (3, 4) or tuple(im.shape) != shape:
+        raise ValueError("the coefficients must be two arrays of one shape, (nz, nrow, R) or (nz, nrow, R, S)")
+    nz, nrow, R = shape[:3]
+    S = shape[3] if len(shape) == 4 else 1
+    out_shape = (S, nrow, nz, nz) if len(shape) == 4 else (nrow, nz, nz)
+    if isinstance(re, _hip.DeviceArray) or isinstance(im, _hip.DeviceArray):
+        if getattr(re, "name", None) != "spec_re" or getattr(im, "name", None) != "spec_im":
+            raise ValueError("device coefficients must be the views power_spectrum(..., coefficients=True, resident=True) returned")
+        ctx = re._owner
+        views = ctx.cross_spectrum_resident(nz, nrow, R, S)
+        if resident:
+            s_re, s_im, coh = (_hip.DeviceArray(v.ptr, out_shape, ctx, v.name) for v in views)
+            return (s_re, s_im), coh
+        s_re, s_im, coh = (ctx.fetch(v.name, out_shape) for v in views)
+    else:
+        if resident:
+            raise ValueError("resident=True needs device coefficients")
+        s_re, s_im, coh = (v.reshape(out_shape) for v in (ctx or _hip.default_context()).cross_spectrum(
+            np.asarray(re, dtype=np.float64).reshape(nz, nrow, R, S), np.asarray(im, dtype=np.float64).reshape(nz, nrow, R, S)))
+    return s_re + 1j * s_im, coh
 
 
 def _torus_graph_weights(N, weights, nboot, seed):

@@ -420,6 +420,49 @@ int gpcsd_plv(gpcsd_ctx *ctx, const double *u_re, const double *u_im, int nz, in
  * (S * nsel * nz * nz doubles each).  Waits for its own work and leaves every other buffer alone.  rc -4 unless the last
  * gpcsd_analytic_resident call stored both halves of the phasors with nz, nsel and M = R * S as given here. */
 int gpcsd_plv_resident(gpcsd_ctx *ctx, int nz, int nsel, int R, int S);
+/* Power spectrum of a field along time, averaged over the trials.  Every step of a periodogram of fixed length but the final modulus
+ * is linear -- window, detrend, zero-padded FFT, scaling -- so it is ONE complex matrix A = A_re + i A_im (nrow, nts), keeping a
+ * frequency keeps a row (gpcsd_amd.utility_functions.spectral_operator builds it).  NO REFERENCE COUNTERPART in the package; usage
+ * note: it replaces the scipy.signal.periodogram(..., detrend=False, axis=1) calls on csd_pred, csd_pred_list, the LFP forms and the
+ * recording and the mean over the trials that follows (auditory_lfp/fit_gpcsd_baseline.py:189-195, neuropixels/fit_gpcsd2d.py:120-128).
+ * x (nz, nts, R, S): R trials, S draws per trial with the draw index innermost (S = 1 for posterior means; gpcsd_sample_posterior's
+ * layout otherwise), m = r S + s:
+ *   X[z, j, m] = sum_t A[j, t] x[z, t, m]                                    (one fp64 MFMA product for both parts)
+ *   power[z, j, r, s] = Re X^2 + Im X^2,     psd[z, j, s] = 1/R sum_r power[z, j, r, s]
+ * psd (nz, nrow, S) is required; power, X_re, X_im (nz, nrow, R, S each) may be NULL and are then neither stored on the device nor
+ * touched.  The sum over the trials runs in a fixed order (per column tile in trial order, then over the tiles of a site) without
+ * atomics: the same call returns the same bits, and psd has the same bits whichever optional outputs are asked for.  Host arrays:
+ * upload, two launches, download.  rc -3: NULL inputs or an empty shape; GPCSD_ERR_CAPACITY (before anything is read): R * S >=
+ * GPCSD_MAX_GEMM_LD_KMAJOR, nts >= 2^22, nz * R * S >= 2^31, nrow * nts >= 2^28. */
+int gpcsd_power_spectrum(gpcsd_ctx *ctx, const double *x, int nz, int nts, int R, int S, const double *A_re, const double *A_im, int nrow,
+                         double *psd, double *power, double *X_re, double *X_im);
+/* Same computation (NO REFERENCE COUNTERPART in the package; usage note as gpcsd_power_spectrum: auditory_lfp/fit_gpcsd_baseline.py:189-195,
+ * neuropixels/fit_gpcsd2d.py:120-128) on a field that is ALREADY in HBM: the named ctx-owned device buffer src_name from src_offset
+ * doubles on (as gpcsd_analytic_resident), read as (nz, nts, R, S).  psd -> "spec_psd" (nz * nrow * S doubles) always; want_mask: bit 0
+ * power -> "spec_power", bit 1 X_re -> "spec_re", bit 2 X_im -> "spec_im" (nz * nrow * R * S doubles each, for gpcsd_fetch /
+ * gpcsd_device_buffer / gpcsd_cross_spectrum_resident); outputs not asked for are not stored.  Collects a queued prediction's
+ * deferred status first (rc > 0 as gpcsd_fetch), waits for its own work and leaves every other buffer alone (the prediction, phase
+ * and PLV buffers among them).  rc -2: no buffer of that name; rc -3: bad arguments, the source is one of the call's buffers, or it
+ * holds fewer than src_offset + nz * nts * R * S doubles; capacity as gpcsd_power_spectrum. */
+int gpcsd_power_spectrum_resident(gpcsd_ctx *ctx, const char *src_name, long src_offset, int nz, int nts, int R, int S, const double *A_re,
+                                  const double *A_im, int nrow, int want_mask);
+/* Cross-spectral matrix and magnitude-squared coherence of ALL site pairs from the coefficients X = X_re + i X_im (nz, nrow, R, S) of
+ * gpcsd_power_spectrum.  NO REFERENCE COUNTERPART in the package; usage note: the amplitude-weighted companion of gpcsd_plv for the
+ * spectra of auditory_lfp/fit_gpcsd_baseline.py:189-195 and neuropixels/fit_gpcsd2d.py:120-128.  For every draw s and kept row j,
+ *   s_re + i s_im [s, j, a, b] = 1/R sum_r X[a] conj(X[b])         = scipy.signal.csd(x_b, x_a) averaged over the trials (SciPy
+ *   coh[s, j, a, b] = (s_re^2 + s_im^2) / (s_re[a, a] s_re[b, b])    conjugates its FIRST argument): the orientation of gpcsd_plv
+ * in the scaling of the operator that made X; the ranks of a trial-sharded job add R (s_re + i s_im) and form coh after the sum.  coh
+ * is 0 where its denominator is 0 (an all-zero site).  Outputs (S, nrow, nz, nz) each, any may be NULL.  The matrix is gpcsd_plv's
+ * kernel on X: s_re and coh are symmetric, s_im antisymmetric BIT FOR BIT, the diagonal of s_im is 0 and that of coh 1 (or 0); fixed
+ * summation order, no atomics.  rc -3: NULL inputs or an empty shape; capacity as gpcsd_plv. */
+int gpcsd_cross_spectrum(gpcsd_ctx *ctx, const double *X_re, const double *X_im, int nz, int nrow, int R, int S, double *s_re, double *s_im,
+                         double *coh);
+/* Same computation (NO REFERENCE COUNTERPART in the package; usage note as gpcsd_cross_spectrum: auditory_lfp/fit_gpcsd_baseline.py:189-195,
+ * neuropixels/fit_gpcsd2d.py:120-128) on the coefficients gpcsd_power_spectrum_resident left in "spec_re" / "spec_im"; results in the
+ * named device buffers "xspec_re", "xspec_im", "xspec_coh" (S * nrow * nz * nz doubles each).  Waits for its own work and leaves every
+ * other buffer alone.  rc -4 unless the last gpcsd_power_spectrum_resident call stored both halves of the coefficients with nz, nrow,
+ * R and S as given here. */
+int gpcsd_cross_spectrum_resident(gpcsd_ctx *ctx, int nz, int nrow, int R, int S);
 /* Solve L^T X = B with the lower Cholesky factor L (n, n): the transposed companion of gpcsd_trsm_lower, same inverted-diagonal-block
  * + GEMM scheme, host arrays, B and X (n, nrhs); L is not modified.  No reference counterpart in the package; it serves
  * gpcsd_torus_graph (auditory_lfp/torus_graph_fit.py, neuropixels/fit_torus_graph.py: phi = L^-T L^-1 H). */
