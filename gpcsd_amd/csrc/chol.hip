@@ -8,14 +8,25 @@
 //      the sub-block on MFMA by all eight waves, then the inverse of the triangular factor by doubling, 16 -> 32 -> 64 -> 128 with
 //      MFMA products -- a 128 x 128 EPI_SUB product between them, and the block inverse assembled from the two sub-block inverses
 //      (X_lowerleft = -X_22 (L21 X_11): two small products);
-//   P  the panel solve L21 = A21 X^T is ONE MFMA GEMM with K = 256 (no triangular solve kernel: trsm by inverted diagonal blocks
-//      is a product);
+//   P  the panel solve L21 = A21 X^T is an MFMA GEMM with K = 256 (no triangular solve kernel: trsm by inverted diagonal blocks
+//      is a product) and one correction step, two more such products (below);
 //   T  the trailing update A22 -= L21 L21^T is a rank-256 MFMA GEMM over the tiles on or below the diagonal only, accumulators
 //      preloaded with -C (EPI_SUB: no second pass over A22); rank 256 is 32 flop per byte of A22, above the fp64 MFMA ridge of ~10.
 // Look-ahead with gates: the next step's D runs on a side stream beside T, which is split by rows into T_b1 / T_b2 behind one-wave
 // gate launches that hold each part back until the diagonal workgroup it has to leave a CU to is resident (under the update's
-// thousands of tiles no CU ever drains by itself).  n = 12 000: 18 ms = 0.40 of the fp64 MFMA peak.
+// thousands of tiles no CU ever drains by itself).  n = 12 000: 21.4 ms = 0.34 of the fp64 MFMA peak (17.7 ms before the
+// panel solve's correction step, below).
 // Triangular solves with many right-hand sides use the same inverted-diagonal-block + GEMM scheme.
+//
+// Accuracy of the explicit inverses.  The doubling X_BA = -X_C (B X_A) is a block forward substitution on the columns of X, so
+// the residual it keeps small is the RIGHT one, L11 X - I (|L11 X - I| <~ u |L11| |X|; the left one, X L11 - I, has no such bound)
+// -- the one the panel solve needs: L21 = A21 X^T gives L21 L11^T - A21 = A21 (L11 X - I)^T.  But u || |L11| |X| || is not u: on a
+// squared-exponential Gram matrix with 1e-8 jitter (condition 5e9) a plain product with X left max |A - L L^T|_ij / sqrt(a_ii a_jj)
+// at 3.8e4 u, 6.8e3 times LAPACK's, and the componentwise backward error of the triangular solves at 5.6e5 (L) / 7.2e5 (L^T) times
+// LAPACK's substitution (tests/test_chol_kernels.py).  So every product with an explicit inverse is followed by ONE correction step
+// with the factor itself -- L21 += (A21 - L21 L11^T) X^T, X_blk += X (B_blk - L11 X_blk): two more products of the same shapes --
+// whose residual is formed with L11, not X: the error that remains is the rounding of that residual, u (|A21| + |L21| |L11^T|), what
+// substitution leaves too.
 #include "kernels.hpp"
 
 namespace gpcsd {
@@ -28,7 +39,9 @@ constexpr int LDW = NBO + 16, LDWS = NB + 16;
 
 // sqrt(d) and 1 / sqrt(d) together from v_rsq_f64 by two coupled Newton (Goldschmidt) steps and one correction of the root: ten
 // dependent operations instead of an IEEE square root followed by an IEEE division (~35), on the serial path of every column
-// step.  Within 1-2 ulp; d <= 0 or non-finite gives NaN / inf as the plain sqrt would (the caller flags d <= 0).
+// step.  Within 1-2 ulp (measured through potrf on diagonal matrices, 512 pivots over [1, 4) and 1e-290 .. 1e290: 0.499 ulp at
+// worst, every root correctly rounded -- tests/test_chol_kernels.py); d <= 0 or non-finite gives NaN / inf as the plain sqrt
+// would (the caller flags d <= 0).
 __device__ __forceinline__ void sqrt_rsqrt(double d, double &root, double &rinv) {
     const double y = __builtin_amdgcn_rsq(d);
     double gq = d * y, h = 0.5 * y;
@@ -137,10 +150,12 @@ __device__ __forceinline__ void inverse_level(double *As, int wid, int lane) {
 // status: first failing pivot + 1 (global index pivot_base + j).  Blocks smaller than 128 are padded with the identity.
 // started (device word, agent-scope store: visible to the other XCDs at once; may be null): stamped with `token` as soon as the workgroup runs -- it then HAS its CU; potrf's gate
 // launches poll the word before they let the trailing update's tiles take every other one (see potrf_device).
+// Lout (may be null; leading dimension ldl): the block's lower triangle with zeros above it, as the kernel read it -- the
+// triangular solves form their residual with it, so that nothing above the diagonal of the caller's L is ever read.
 template <bool FACTOR>
 __global__ __launch_bounds__(DNT) void diag128_kernel(double *Ablk, long lda, int nb, double *Xout, long ldx, int *status,
                                                        int pivot_base, unsigned long long *clk, unsigned int *started,
-                                                       unsigned int token) {
+                                                       unsigned int token, double *Lout, long ldl) {
     __builtin_amdgcn_s_setprio(3);
     if (started && threadIdx.x == 0) __hip_atomic_store(started, token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // clk (measurement aid, normally null): wall-clock stamps (100 MHz) at the phase boundaries -- [0] start, [1] block loaded,
@@ -277,13 +292,17 @@ __global__ __launch_bounds__(DNT) void diag128_kernel(double *Ablk, long lda, in
     stamp(8);
     for (int e = tid; e < DN * DN; e += DNT) {
         const int i = e >> 7, c = e & 127;
-        if (i < nb && c < nb) Xout[(long)i * ldx + c] = c <= i ? As[c * DLD + i + 1] : 0.0;
+        if (i < nb && c < nb) {
+            Xout[(long)i * ldx + c] = c <= i ? As[c * DLD + i + 1] : 0.0;
+            if (Lout) Lout[(long)i * ldl + c] = c <= i ? As[i * DLD + c] : 0.0;
+        }
     }
     stamp(9);
 }
 
 static void launch_diag(double *Ablk, long lda, int nb, double *Xout, long ldx, int *status, int pivot_base, bool factor,
-                        hipStream_t s, unsigned long long *clk = nullptr, unsigned int *started = nullptr, unsigned int token = 0) {
+                        hipStream_t s, unsigned long long *clk = nullptr, unsigned int *started = nullptr, unsigned int token = 0,
+                        double *Lout = nullptr, long ldl = 0) {
     static PerDeviceOnce attr_once;
     if (attr_once.first()) {
         GP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(diag128_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -293,10 +312,10 @@ static void launch_diag(double *Ablk, long lda, int nb, double *Xout, long ldx, 
     }
     if (factor)
         hipLaunchKernelGGL(diag128_kernel<true>, dim3(1), dim3(DNT), DIAG_LDS_BYTES, s, Ablk, lda, nb, Xout, ldx, status, pivot_base, clk,
-                           started, token);
+                           started, token, Lout, ldl);
     else
         hipLaunchKernelGGL(diag128_kernel<false>, dim3(1), dim3(DNT), DIAG_LDS_BYTES, s, Ablk, lda, nb, Xout, ldx, status, pivot_base, clk,
-                           started, token);
+                           started, token, Lout, ldl);
 }
 
 __global__ void copy2d_kernel(const double *__restrict__ src, long lds_, double *__restrict__ dst, long ldd, int rows, int cols) {
@@ -378,6 +397,10 @@ __global__ __launch_bounds__(64) void gate_kernel(unsigned int *flag, unsigned i
 static void factor_diag_block(gpcsd_ctx *c, double *Ablk, long ld, int nb, double *X, double *tmp, double *Wsub, int *d_status,
                               int pivot_base, hipStream_t s, unsigned int first_token = 0) {
     ProfScope ps(c, "potrf_diag_block", (double)nb * nb * nb * (1.0 / 3.0 + 1.0 / 3.0), s);
+    // zeros above the second sub-block (the diagonal kernel zeroes the rest above the diagonal): the panel solve's correction
+    // step then multiplies by this block as a whole.  The caller's upper triangle is overwritten -- potrf zeroes all of it in the
+    // end anyway -- and still never read.
+    if (nb > NB) GP_HIP(hipMemset2DAsync(Ablk + NB, (size_t)ld * sizeof(double), 0, (size_t)(nb - NB) * sizeof(double), NB, s));
     for (int p0 = 0; p0 < nb; p0 += NB) {
         const int b = std::min(NB, nb - p0), rows = nb - (p0 + b);
         double *App = Ablk + (long)p0 * ld + p0;
@@ -385,8 +408,17 @@ static void factor_diag_block(gpcsd_ctx *c, double *Ablk, long ld, int nb, doubl
                     first_token ? c->h_chol_flag : nullptr, first_token + (unsigned)(p0 / NB));
         if (rows > 0) {
             double *A21 = Ablk + (long)(p0 + b) * ld + p0;
-            // L21 = A21 X_pp^T (into Wsub; copied into place below), A22 -= L21 L21^T -- all inside the diagonal block
+            // L21 = A21 X_pp^T (into Wsub; copied into place below) with its correction step L21 += (A21 - L21 L_pp^T) X_pp^T
+            // (see the header; the residual takes A21's place, which L21 overwrites later), A22 -= L21 L21^T -- all inside the
+            // diagonal block
             small_gemm(c, rows, b, b, A21, ld, X + (long)p0 * NBO + p0, NBO, true, Wsub, LDWS, 1.0, EPI_STORE, "potrf_blk_panel", s);
+            GemmDesc r;
+            r.M = rows; r.N = b; r.K = b;
+            r.A = Wsub; r.lda = LDWS; r.B = App; r.ldb = ld; r.transB = true; r.C = A21; r.ldc = ld;
+            r.epi = EPI_SUB; r.prio = 1; r.cfg = small_cfg();
+            r.prof_name = "potrf_blk_panel";
+            gemm_f64(c, r, s);
+            small_gemm(c, rows, b, b, A21, ld, X + (long)p0 * NBO + p0, NBO, true, Wsub, LDWS, 1.0, EPI_ACCUM, "potrf_blk_panel", s);
             GemmDesc g;
             g.M = rows; g.N = rows; g.K = b;
             g.A = Wsub; g.lda = LDWS; g.B = Wsub; g.ldb = LDWS; g.transB = true;
@@ -394,14 +426,12 @@ static void factor_diag_block(gpcsd_ctx *c, double *Ablk, long ld, int nb, doubl
             g.epi = EPI_SUB; g.lower = true; g.prio = 1; g.cfg = small_cfg();
             g.prof_name = "potrf_blk_syrk";
             gemm_f64(c, g, s);
-            if (nb > 2 * NB)             // (more than two sub-blocks: the next sub-step reuses Wsub -- L21 into its place now)
-                hipLaunchKernelGGL(copy2d_kernel, dim3(ceil_div((long)rows * b, 256)), dim3(256), 0, s, (const double *)Wsub, (long)LDWS,
-                                   A21, ld, rows, b);
         }
     }
-    if (nb > NB && nb <= 2 * NB) {
-        // two sub-blocks (the usual 256): the inverse's lower-left block reads L21 from the panel buffer, and the copy of L21
-        // into its place comes last -- one dependent launch less in front of the panel solve that waits for this chain
+    if (nb > NB) {
+        // two sub-blocks (the usual 256; nb <= NBO = 2 NB at every call, so Wsub is written once): the inverse's lower-left block
+        // reads L21 from the panel buffer, and the copy of L21 into its place comes last -- one dependent launch less in front of
+        // the panel solve that waits for this chain
         assemble_block_inverse(c, Ablk, ld, nb, X, tmp, s, Wsub, LDWS);
         hipLaunchKernelGGL(copy2d_kernel, dim3(ceil_div((long)(nb - NB) * NB, 256)), dim3(256), 0, s, (const double *)Wsub, (long)LDWS,
                            Ablk + (long)NB * ld, ld, nb - NB, NB);
@@ -454,6 +484,16 @@ void potrf_device(gpcsd_ctx *c, double *A, int n, int *d_status, hipStream_t s_i
             p.M = m; p.N = nb; p.K = nb;
             p.A = A21; p.lda = n; p.B = X; p.ldb = NBO; p.transB = true; p.C = W; p.ldc = LDW;
             p.prof_name = "potrf_panel";
+            gemm_f64(c, p, s);
+            // one correction step W += (A21 - W L11^T) X^T (see the header).  The residual takes A21's place (L21 overwrites it
+            // below); L11 is read as a full nb x nb block: factor_diag_block has put zeros above its diagonal blocks.
+            GemmDesc r;
+            r.M = m; r.N = nb; r.K = nb;
+            r.A = W; r.lda = LDW; r.B = A + (long)k0 * n + k0; r.ldb = n; r.transB = true; r.C = A21; r.ldc = n;
+            r.epi = EPI_SUB;
+            r.prof_name = "potrf_panel";
+            gemm_f64(c, r, s);
+            p.epi = EPI_ACCUM;
             gemm_f64(c, p, s);
         }
         const int na = std::min(NBO, m);                               // T_a: the next panel's columns (all rows)
@@ -537,20 +577,34 @@ void trsm_lower_device(gpcsd_ctx *c, const double *L, int n, double *B, int nrhs
     double *X = c->buf<double>("chol_Linv", (size_t)NBO * NBO);
     double *tmp = c->buf<double>("chol_inv_tmp", (size_t)NBO * NBO);
     double *Xb = c->buf<double>("trsm_xblk", (size_t)NBO * nrhs);
+    double *Ld = c->buf<double>("chol_Ldiag", (size_t)NBO * NBO);     // the NB x NB diagonal blocks of L11, zeros above the diagonal
     for (int k0 = 0; k0 < n; k0 += NBO) {
         const int nb = std::min(NBO, n - k0);
         const double *Lkk = L + (long)k0 * n + k0;
+        double *Bblk = B + (long)k0 * nrhs;
         for (int p0 = 0; p0 < nb; p0 += NB)
             launch_diag(const_cast<double *>(Lkk) + (long)p0 * n + p0, (long)n, std::min(NB, nb - p0), X + (long)p0 * NBO + p0, (long)NBO,
-                        nullptr, 0, false, s);
+                        nullptr, 0, false, s, nullptr, nullptr, 0, Ld + (long)p0 * NBO + p0, (long)NBO);
         assemble_block_inverse(c, Lkk, n, nb, X, tmp, s);
         // X_blk = inv(L11) B_blk (the strictly upper part of the inverse buffer is stale: zero it through K-limited products)
         // -- row block i of the inverse has its non-zeros in columns [0, NB (i + 1)): one product per NB-row block
+        auto apply_inverse = [&](int epi) {
+            for (int p0 = 0; p0 < nb; p0 += NB) {
+                const int b = std::min(NB, nb - p0);
+                small_gemm(c, b, nrhs, p0 + b, X + (long)p0 * NBO, NBO, Bblk, nrhs, false, Xb + (long)p0 * nrhs, nrhs, 1.0, epi, "trsm_gemm", s);
+            }
+        };
+        apply_inverse(EPI_STORE);
+        // one correction step X_blk += inv(L11) (B_blk - L11 X_blk) (see the header): the residual takes B_blk's place, row block
+        // by row block from the blocks of L left of the diagonal and the diagonal block's clean copy
         for (int p0 = 0; p0 < nb; p0 += NB) {
             const int b = std::min(NB, nb - p0);
-            small_gemm(c, b, nrhs, p0 + b, X + (long)p0 * NBO, NBO, B + (long)k0 * nrhs, nrhs, false, Xb + (long)p0 * nrhs, nrhs, 1.0,
-                       EPI_STORE, "trsm_gemm", s);
+            if (p0 > 0)
+                small_gemm(c, b, nrhs, p0, Lkk + (long)p0 * n, n, Xb, nrhs, false, Bblk + (long)p0 * nrhs, nrhs, -1.0, EPI_ACCUM, "trsm_gemm", s);
+            small_gemm(c, b, nrhs, b, Ld + (long)p0 * NBO + p0, NBO, Xb + (long)p0 * nrhs, nrhs, false, Bblk + (long)p0 * nrhs, nrhs, -1.0,
+                       EPI_ACCUM, "trsm_gemm", s);
         }
+        apply_inverse(EPI_ACCUM);
         hipLaunchKernelGGL(copy2d_kernel, dim3(ceil_div((long)nb * nrhs, 256)), dim3(256), 0, s, (const double *)Xb, (long)nrhs,
                            B + (long)k0 * nrhs, (long)nrhs, nb, nrhs);
         const int rows = n - (k0 + nb);
@@ -570,6 +624,7 @@ void trsm_lower_trans_device(gpcsd_ctx *c, const double *L, int n, double *B, in
     double *X = c->buf<double>("chol_Linv", (size_t)NBO * NBO);
     double *tmp = c->buf<double>("chol_inv_tmp", (size_t)NBO * NBO);
     double *Xb = c->buf<double>("trsm_xblk", (size_t)NBO * nrhs);
+    double *Ld = c->buf<double>("chol_Ldiag", (size_t)NBO * NBO);
     auto gemm_ta = [&](int M, int N, int K, const double *A, long lda, const double *Bm, double *C, double alpha, int epi) {
         GemmDesc g;
         g.M = M; g.N = N; g.K = K;
@@ -583,14 +638,27 @@ void trsm_lower_trans_device(gpcsd_ctx *c, const double *L, int n, double *B, in
     for (int k0 = last; k0 >= 0; k0 -= NBO) {
         const int nb = std::min(NBO, n - k0);
         const double *Lkk = L + (long)k0 * n + k0;
+        double *Bblk = B + (long)k0 * nrhs;
         for (int p0 = 0; p0 < nb; p0 += NB)
             launch_diag(const_cast<double *>(Lkk) + (long)p0 * n + p0, (long)n, std::min(NB, nb - p0), X + (long)p0 * NBO + p0, (long)NBO,
-                        nullptr, 0, false, s);
+                        nullptr, 0, false, s, nullptr, nullptr, 0, Ld + (long)p0 * NBO + p0, (long)NBO);
         assemble_block_inverse(c, Lkk, n, nb, X, tmp, s);
+        auto apply_inverse = [&](int epi) {
+            for (int p0 = 0; p0 < nb; p0 += NB) {
+                const int b = std::min(NB, nb - p0);
+                gemm_ta(b, nrhs, nb - p0, X + (long)p0 * NBO + p0, NBO, Bblk + (long)p0 * nrhs, Xb + (long)p0 * nrhs, 1.0, epi);
+            }
+        };
+        apply_inverse(EPI_STORE);
+        // one correction step X_blk += Xkk^T (B_blk - L_kk^T X_blk): row block p0 of L_kk^T is the diagonal block's clean copy and
+        // the blocks of L below it, both read transposed; the residual takes B_blk's place
         for (int p0 = 0; p0 < nb; p0 += NB) {
-            const int b = std::min(NB, nb - p0);
-            gemm_ta(b, nrhs, nb - p0, X + (long)p0 * NBO + p0, NBO, B + (long)(k0 + p0) * nrhs, Xb + (long)p0 * nrhs, 1.0, EPI_STORE);
+            const int b = std::min(NB, nb - p0), below = nb - (p0 + b);
+            gemm_ta(b, nrhs, b, Ld + (long)p0 * NBO + p0, NBO, Xb + (long)p0 * nrhs, Bblk + (long)p0 * nrhs, -1.0, EPI_ACCUM);
+            if (below > 0)
+                gemm_ta(b, nrhs, below, Lkk + (long)(p0 + b) * n + p0, n, Xb + (long)(p0 + b) * nrhs, Bblk + (long)p0 * nrhs, -1.0, EPI_ACCUM);
         }
+        apply_inverse(EPI_ACCUM);
         hipLaunchKernelGGL(copy2d_kernel, dim3(ceil_div((long)nb * nrhs, 256)), dim3(256), 0, s, (const double *)Xb, (long)nrhs,
                            B + (long)k0 * nrhs, (long)nrhs, nb, nrhs);
         if (k0 > 0)                                       // B[above] -= L[k0 : k0 + nb, 0 : k0]^T X_blk

@@ -553,10 +553,12 @@ void k_fwdR_grad(gpcsd_ctx *c, const double *S, const double *x, int nx, const d
                  int B = 1, long s_out = 0);
 
 // ---------------------------------------------------------------- Cholesky (chol.hip)
-// In-place lower Cholesky of A (n,n) row-major; strictly-upper part zeroed.  d_status: 0 ok, k+1 = pivot k <= 0.
+// In-place lower Cholesky of A (n,n) row-major; strictly-upper part zeroed.  d_status: 0 ok, k+1 = pivot k <= 0 or NaN (the first
+// such k, whichever block or look-ahead step meets it).  Only the lower triangle of A is read: whatever lies above the diagonal,
+// NaN included, leaves the factor's bits unchanged (tests/test_chol_kernels.py).
 void potrf_device(gpcsd_ctx *c, double *A, int n, int *d_status, hipStream_t s);
 void potrf_diag128_probe(gpcsd_ctx *c, double *A, int n, double *X, int *d_status, unsigned long long *clk_dev, hipStream_t s);
-// X = L^{-1} B in place (B (n,nrhs) row-major)
+// X = L^{-1} B in place (B (n,nrhs) row-major).  Both solves read the lower triangle of L only.
 void trsm_lower_device(gpcsd_ctx *c, const double *L, int n, double *B, int nrhs, hipStream_t s);
 // X = L^{-T} B in place (the transposed solve of the same factor; B (n,nrhs) row-major)
 void trsm_lower_trans_device(gpcsd_ctx *c, const double *L, int n, double *B, int nrhs, hipStream_t s);
