@@ -144,6 +144,8 @@ SIGNATURES = {
     "gpcsd_debug_gemm": (_I, [_P, ctypes.POINTER(DebugGemmArgs)]),
     "gpcsd_eig_D": (_I, [_P, _DP, _I, _DP, _I, _DP, _I, _DP, _DP, _DP]),
     "gpcsd_whitened_quad": (_I, [_P, _DP, _I, _DP, _I, _DP, _DP, _I, _DP]),
+    "gpcsd_shift_plan": (_I, [_P, _DP, _I, _DP, _I, _DP, _DP, _I, _DP, _I, _DP]),
+    "gpcsd_shift_eval": (_I, [_P, ctypes.POINTER(_I), _DP, _I, _D, _D, _DP, _DP]),
     "gpcsd_debug_sytrd": (_I, [_P, _DP, _I, _DP, _DP, _DP, _DP]),
     "gpcsd_debug_stedc": (_I, [_P, _DP, _DP, _I, _DP, _DP]),
     "gpcsd_debug_ll_tridiag": (_I, [_P, _DP, _DP, _I, _I, _I, _DP, _DP, _D, _I, _I, _DP, _DP, _D, _I, _I, _D, _I, _DP, _DP]),
@@ -411,6 +413,8 @@ class Context:
         self.device = int(device)
         self._keep = []
         self.phasor_generation = 0       # analytic_resident calls so far: whose unit phasors "phasor_re" / "phasor_im" hold
+        self.shift_generation = 0        # shift_plan calls so far: whose plan the "shift_*" buffers hold
+        self._shift_shape = None         # (nx, nt, ntrials, nseg) of that plan
 
     def close(self):
         if getattr(self, "_h", None):
@@ -766,6 +770,47 @@ class Context:
         out = np.empty(resid.shape[2])
         self._check(self._lib.gpcsd_whitened_quad(self._h, _ptr(Qs), nx, _ptr(Qt), nt, _ptr(Dv), _ptr(resid), resid.shape[2], _ptr(out)))
         return out
+
+    def shift_plan(self, Qs, Qt, Dvec, lfp, mu, t):
+        """Upload everything the trial-shift objective needs, once (gpcsd_shift_plan): the decomposition (Qs, Qt, Dvec), the trials
+        lfp (nx, nt, ntrials), the means mu (nx, nt, nseg + 1) -- background first -- and the strictly increasing time grid t.
+        Returns the plan's generation: `shift_generation` moves on with every plan, a context holds one at a time."""
+        Qs, Qt = _arr(Qs), _arr(Qt)
+        nx, nt = Qs.shape[0], Qt.shape[0]
+        lfp = np.ascontiguousarray(np.atleast_3d(np.asarray(lfp, dtype=np.float64)))
+        mu = _arr(mu)
+        if lfp.shape[:2] != (nx, nt) or mu.ndim != 3 or mu.shape[:2] != (nx, nt) or mu.shape[2] < 2:
+            raise ValueError("lfp has shape %s and mu %s, expected (%d, %d, ntrials) and (%d, %d, nseg + 1)"
+                             % (lfp.shape, mu.shape, nx, nt, nx, nt))
+        Dv = _arr(np.asarray(Dvec, dtype=np.float64).reshape(-1), (nx * nt,), "Dvec")
+        t = _arr(np.asarray(t, dtype=np.float64).reshape(-1), (nt,), "t")
+        nseg = mu.shape[2] - 1
+        self._shift_shape = None
+        self._check(self._lib.gpcsd_shift_plan(self._h, _ptr(Qs), nx, _ptr(Qt), nt, _ptr(Dv), _ptr(lfp), lfp.shape[2], _ptr(mu), nseg, _ptr(t)))
+        self._shift_shape = (nx, nt, lfp.shape[2], nseg)
+        self.shift_generation += 1
+        return self.shift_generation
+
+    def shift_eval(self, trials, taus, grad=True, mutau=0.0, sigtau=10.0):
+        """(f (B,), g (B, nseg) or None) of the plan's objective at the B points (trials[b], taus[b]) (gpcsd_shift_eval); only the
+        points and the results cross PCIe.  Long batches go in chunks that respect the library's operand limits and keep the two
+        work buffers within 256 MiB each: a point's bits do not depend on its chunk."""
+        trials = np.ascontiguousarray(np.asarray(trials).reshape(-1), dtype=np.intc)
+        if self._shift_shape is None:
+            nseg, chunk = max(1, np.size(taus) // max(trials.size, 1)), max(trials.size, 1)
+        else:
+            nx, nt, _, nseg = self._shift_shape
+            chunk = max(1, min((MAX_GEMM_LD_KMAJOR - 1) // nt, (1 << 25) // (nx * nt), ((1 << 31) - 1) // (max(nseg * nt, nx))))
+        taus = _arr(np.asarray(taus, dtype=np.float64).reshape(-1, nseg), (trials.size, nseg), "taus")
+        if trials.size == 0:
+            raise ValueError("no points")
+        f = np.empty(trials.size)
+        g = np.empty((trials.size, nseg)) if grad else None
+        for lo in range(0, trials.size, chunk):
+            tr, ta = trials[lo:lo + chunk], taus[lo:lo + chunk]
+            self._check(self._lib.gpcsd_shift_eval(self._h, tr.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _ptr(ta), tr.size, float(mutau),
+                                                   float(sigtau), _ptr(f[lo:lo + chunk]), _ptr(g[lo:lo + chunk]) if grad else None))
+        return f, g
 
     def potrf(self, A):
         A = _arr(A)

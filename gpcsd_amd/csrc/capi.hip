@@ -1415,6 +1415,7 @@ extern "C" int gpcsd_set_time(gpcsd_ctx *c, const double *t, int nt) {
 #include "capi_masked.inl"
 #include "capi_phase.inl"
 #include "capi_spectrum.inl"
+#include "capi_shift.inl"
 #include "capi_torus.inl"
 #include "capi_grad.inl"
 #include "capi_measure.inl"

@@ -222,6 +222,9 @@ struct gpcsd_ctx {
     // shape (nz, nrow, R, S) of the coefficients the last gpcsd_power_spectrum_resident left in "spec_re" / "spec_im" (0: none, or
     // only one of the two): what gpcsd_cross_spectrum_resident may read
     long spec_shape[4] = {0, 0, 0, 0};
+    // shape (nx, nt, ntrials, nseg) of the trial-shift plan gpcsd_shift_plan left in the "shift_*" buffers (0: none): what
+    // gpcsd_shift_eval evaluates
+    int shift_shape[4] = {0, 0, 0, 0};
     gpcsd::SymDev sym_s, sym_t;             // reflection symmetry of the electrode / time grids (ns == 0: none found)
     // folded-basis GEMMs (capi.hip): what the electrode symmetry reflects about, host copies of the grids to recognise
     // prediction sites / times with the same symmetry, the symmetry of the last prediction sites, and whether the

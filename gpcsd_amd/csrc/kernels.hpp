@@ -565,4 +565,31 @@ void trsm_lower_trans_device(gpcsd_ctx *c, const double *L, int n, double *B, in
 void logdet_chol_device(gpcsd_ctx *c, const double *L, int n, double *out, hipStream_t s);
 void sumsq_device(gpcsd_ctx *c, const double *x, long n, double *out, hipStream_t s);
 
+// ---------------------------------------------------------------- trial-shift objective and gradient (shift.hip)
+// The tables of a plan and the B points (trial_b, tau_b) of one evaluation.  mu [x][c][k], c = 0 the background and c = i + 1
+// component i; slope [i][x][k], k < nt - 1; lfp [x][trial][k]; lo, dt [b][i][k]; every field [x][b][k] (the flat GEMM layout).
+struct ShiftDesc {
+    int nx = 0, nt = 0, ntrials = 0, nseg = 0, B = 0;
+    const double *t = nullptr, *mu = nullptr, *slope = nullptr, *lfp = nullptr, *D = nullptr;
+    const int *trial = nullptr;      // [B]
+    const double *tau = nullptr;     // [B][nseg]
+    int *lo = nullptr;
+    double *dt = nullptr;
+    double mutau = 0.0, sigtau = 1.0;
+};
+constexpr int SHIFT_MAX_NSEG = 32;   // (= GPCSD_MAX_SHIFT_NSEG) the gradient kernel keeps one partial sum per component in registers
+// slope[i][x][k] = (y_i[x][k+1] - y_i[x][k]) / (t[k+1] - t[k])
+void k_shift_slopes(gpcsd_ctx *c, const double *mu, const double *t, int nx, int nt, int nseg, double *slope, hipStream_t s);
+// lo = clip(searchsorted_left(t, t_k + tau_i), 1, nt - 1) - 1 and dt = (t_k + tau_i) - t_lo for every (b, i, k)
+void k_shift_locate(gpcsd_ctx *c, const ShiftDesc &d, hipStream_t s);
+// R[x][b][k] = lfp[x][trial_b][k] - (mu_0[x][k] + sum_i y_i[x][lo] + slope_i[x][lo] dt)
+void k_shift_resid(gpcsd_ctx *c, const ShiftDesc &d, double *R, hipStream_t s);
+// workgroups per point of the two reducing kernels (slabs of electrodes; a function of nx alone): the length of a point's partials
+int shift_slabs(int nx);
+// beta = alpha / D (not stored when beta == nullptr), f[b] = 1/2 sum alpha beta + 1/2 sum_i ((tau_i - mutau) / sigtau)^2;
+// part: B * shift_slabs(nx) doubles of scratch
+void k_shift_quad(gpcsd_ctx *c, const ShiftDesc &d, const double *alpha, double *beta, double *part, double *f, hipStream_t s);
+// g[b][i] = -sum_{x,k} Z[x][b][k] slope_i[x][lo(b,i,k)] + (tau_i - mutau) / sigtau^2; part: B * shift_slabs(nx) * nseg doubles
+void k_shift_grad(gpcsd_ctx *c, const ShiftDesc &d, const double *Z, double *part, double *g, hipStream_t s);
+
 }  // namespace gpcsd

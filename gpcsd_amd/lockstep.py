@@ -3,7 +3,8 @@
 fit() runs independent L-BFGS-B restarts (reference: gpcsd1d.py:193-220, gpcsd2d.py:230-262) and the trial-shift fits of
 auditory_lfp/fit_mean_function.py:323-328 run one L-BFGS-B per trial.  Each chain asks for one objective evaluation at a
 time, and on the GPU one evaluation is a latency-bound chain of small launches -- but k evaluations submitted together cost
-about the same latency as one (gpcsd_loglik_grad_batch, gpcsd_whitened_quad).  The chains stay unmodified SciPy optimisers,
+about the same latency as one (gpcsd_loglik_grad_batch, gpcsd_whitened_quad; gpcsd_shift_eval, which also returns every point's
+analytic gradient: fit_trial_shifts(jac=True)).  The chains stay unmodified SciPy optimisers,
 each on its own thread; their objective callbacks rendezvous here, and when every live chain has submitted its point ONE
 batched evaluation serves them all.
 """

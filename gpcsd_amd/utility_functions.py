@@ -6,7 +6,8 @@ eigendecompositions + the D vector).  analytic_operator, band_phase, plv, plv_fr
 the band-pass + Hilbert + phase-locking step the reference's analysis scripts end with, as one linear operator (host) and two HIP
 launches (csrc/phase.hip); torus_graph, the conditional phase coupling those scripts fit next, likewise (csrc/torus.hip);
 spectral_operator, power_spectrum, cross_spectrum, spectrum_from_sums: the periodogram those scripts take of every prediction, its
-mean over the trials and the coherence of all site pairs (csrc/spectrum.hip)."""
+mean over the trials and the coherence of all site pairs (csrc/spectrum.hip); trial_shift_objective: the objective of the per-trial
+shift fits those scripts run (auditory_lfp/fit_mean_function.py:306-321) with its analytic gradient (csrc/shift.hip)."""
 import numpy as np
 
 from . import _hip
@@ -414,8 +415,32 @@ def torus_graph(phases_or_phasors, weights=None, nboot=0, seed=None, inference=T
     return _torus_graph_result(res, u_re.shape[0], inference)
 
 
+def trial_shift_objective(evec_s, evec_t, Dvec, lfp_trials, mu_lfp, t, mutau=0.0, sigtau=10.0, ctx=None):
+    """The trial-shift objective of auditory_lfp/fit_mean_function.py:306-321 and its analytic gradient, resident on the device.
+    Arguments as `fit_trial_shifts`.  Everything is uploaded once (`Context.shift_plan`); returns a callable
+    `obj(trials, taus, grad=True) -> (f (B,), g (B, nseg) or None)` for B points (trial index, tau (nseg,)) per call, any trial any
+    number of times -- only the points and the results cross PCIe.
+
+        mean(tau)[x, k] = mu[x, k, 0] + sum_i interp1d(t, mu[:, :, i], fill_value="extrapolate")(t_k + tau_i)
+        f = 1/2 sum((evec_s.T @ r @ evec_t)**2 / Dvec) + 1/2 sum(((tau - mutau) / sigtau)**2),   r = lfp_trials[:, :, trial] - mean(tau)
+
+    Between the knots of the interpolation f is exactly quadratic in tau; g is its derivative on the segments the interpolation itself
+    uses, i.e. the LEFT derivative at a tau that puts samples on knots (tau = 0 is such a point: SciPy's segment search puts a sample
+    on a knot into the segment to its left).  A context holds one plan: the callable refuses to run once another plan has replaced
+    its own.  ctx: the `_hip.Context` to plan on (default: the process-wide one)."""
+    ctx = ctx or _hip.default_context()
+    gen = ctx.shift_plan(evec_s, evec_t, Dvec, lfp_trials, mu_lfp, t)
+    mutau, sigtau = float(mutau), float(sigtau)
+
+    def obj(trials, taus, grad=True):
+        if ctx.shift_generation != gen:
+            raise RuntimeError("trial_shift_objective: a later plan on the same context has replaced this one")
+        return ctx.shift_eval(trials, taus, grad=grad, mutau=mutau, sigtau=sigtau)
+    return obj
+
+
 def fit_trial_shifts(evec_s, evec_t, Dvec, lfp_trials, mu_lfp, t, tau0=None, mutau=0.0, sigtau=10.0, width=None,
-                     options=None):
+                     options=None, jac=False, return_evals=False):
     """Per-trial time shifts of the evoked components: the optimisation loop of auditory_lfp/fit_mean_function.py:299-335
     (one L-BFGS-B per trial over `tau`, objective = 0.5 * whitened quadratic form of `lfp_trial - mean(tau)` + Gaussian
     prior on the shifts), with every trial's optimiser running in lock-step so that ONE batched GPU call
@@ -424,7 +449,12 @@ def fit_trial_shifts(evec_s, evec_t, Dvec, lfp_trials, mu_lfp, t, tau0=None, mut
 
     evec_s, evec_t, Dvec: outputs of `comp_eig_D`;  lfp_trials (nx, nt, ntrials);  mu_lfp (nx, nt, nseg + 1): background in
     [..., 0], component means in [..., 1:];  t (nt,) or (nt, 1);  width: chains alive at a time (default min(ntrials, 128),
-    memory-capped).  Returns (tau_hat (ntrials, nseg), success, messages)."""
+    memory-capped).  Returns (tau_hat (ntrials, nseg), success, messages).
+
+    jac=True: the chains are `scipy.optimize.minimize(..., jac=True, method="l-bfgs-b")` on `trial_shift_objective` -- the shifted
+    means, the residuals, the objective and its analytic gradient all stay on the device, one call per lock-step batch, and an
+    iteration costs one evaluation instead of the nseg + 1 of SciPy's finite differences.  return_evals=True appends
+    {"batches", "points"}: the batched evaluations issued and the points they covered."""
     import numpy as np
     import scipy.interpolate
     import scipy.optimize
@@ -433,31 +463,40 @@ def fit_trial_shifts(evec_s, evec_t, Dvec, lfp_trials, mu_lfp, t, tau0=None, mut
     nx, nt, ntrials = lfp_trials.shape
     nseg = mu_lfp.shape[2] - 1
     tt = np.asarray(t, dtype=np.float64).reshape(-1)
-    mu_f = [scipy.interpolate.interp1d(tt, mu_lfp[:, :, i], axis=1, fill_value="extrapolate") for i in range(1, nseg + 1)]
     tau0 = np.zeros(nseg) if tau0 is None else np.asarray(tau0, dtype=np.float64)
+    if jac:
+        obj = trial_shift_objective(evec_s, evec_t, Dvec, lfp_trials, mu_lfp, tt, mutau=mutau, sigtau=sigtau)
 
-    def batch_fn(items):                     # items: [(trial, tau)] -> {trial: objective}
-        resid = np.empty((nx, nt, len(items)))
-        for j, (ti, tau) in enumerate(items):
-            mu = np.array(mu_lfp[:, :, 0], dtype=np.float64, copy=True)
-            for i in range(nseg):
-                mu += mu_f[i](tt + tau[i])
-            resid[:, :, j] = lfp_trials[:, :, ti] - mu
-        quad = whitened_quadratic_forms(evec_s, evec_t, Dvec, resid)
-        return {ti: float(0.5 * quad[j] + 0.5 * np.sum(np.square((np.asarray(tau) - mutau) / sigtau)))
-                for j, (ti, tau) in enumerate(items)}
+        def batch_fn(items):                 # items: [(trial, tau)] -> {trial: (objective, gradient)}
+            f, g = obj([ti for ti, _ in items], np.array([tau for _, tau in items], dtype=np.float64).reshape(len(items), nseg))
+            return {ti: (float(f[j]), g[j].copy()) for j, (ti, _) in enumerate(items)}
+    else:
+        mu_f = [scipy.interpolate.interp1d(tt, mu_lfp[:, :, i], axis=1, fill_value="extrapolate") for i in range(1, nseg + 1)]
+
+        def batch_fn(items):                 # items: [(trial, tau)] -> {trial: objective}
+            resid = np.empty((nx, nt, len(items)))
+            for j, (ti, tau) in enumerate(items):
+                mu = np.array(mu_lfp[:, :, 0], dtype=np.float64, copy=True)
+                for i in range(nseg):
+                    mu += mu_f[i](tt + tau[i])
+                resid[:, :, j] = lfp_trials[:, :, ti] - mu
+            quad = whitened_quadratic_forms(evec_s, evec_t, Dvec, resid)
+            return {ti: float(0.5 * quad[j] + 0.5 * np.sum(np.square((np.asarray(tau) - mutau) / sigtau)))
+                    for j, (ti, tau) in enumerate(items)}
 
     def chain(ti, evaluate):
-        # keyed by the trial: the evaluator hands every chain the value of ITS point of the batch
-        return scipy.optimize.minimize(lambda tau: evaluate(np.array(tau, copy=True)), tau0, method="l-bfgs-b",
-                                       options=options or {})
+        # keyed by the trial: the evaluator hands every chain the value of ITS point of the batch (with jac: value and gradient)
+        return scipy.optimize.minimize(lambda tau: evaluate(np.array(tau, copy=True)), tau0, jac=True if jac else None,
+                                       method="l-bfgs-b", options=options or {})
     if width is None:
         # one OS thread and one (nx, nt) residual per live chain: at most 128 chains, within a 1 GiB budget for the batch's
-        # residuals; the remaining trials wait in run_chains' queue and take the slot of a chain that converges
+        # residuals (with jac no residual leaves the device, the same width keeps the two paths' batches alike); the remaining
+        # trials wait in run_chains' queue and take the slot of a chain that converges
         width = int(max(1, min(ntrials, 128, (1 << 30) // max(8 * nx * nt, 1))))
     out, _ev = run_chains(list(range(ntrials)), chain, lambda items: batch_fn([(k, x) for k, x in items]), width)
     for r in out.values():
         if isinstance(r, Exception):
             raise r
     tau_hat = np.array([out[i].x for i in range(ntrials)])
-    return tau_hat, np.array([bool(out[i].success) for i in range(ntrials)]), [out[i].message for i in range(ntrials)]
+    res = (tau_hat, np.array([bool(out[i].success) for i in range(ntrials)]), [out[i].message for i in range(ntrials)])
+    return res + ({"batches": _ev.batches, "points": _ev.points},) if return_evals else res

@@ -51,6 +51,9 @@ extern "C" {
 /*   GPCSD_MAX_MISSING         missing samples of ONE trial in gpcsd_predict_masked / gpcsd_loglik_masked (m of gpcsd_masked_gram):
  *                           the Schur complement of the missing set is a dense m x m matrix, 512 MB of fp64 at the limit       */
 #define GPCSD_MAX_MISSING         8192
+/*   GPCSD_MAX_SHIFT_NSEG      shifted components of gpcsd_shift_plan (its gradient kernel keeps one partial sum per component in
+ *                           registers; the reference's data has 10-20 per probe)                                                */
+#define GPCSD_MAX_SHIFT_NSEG      32
 #define GPCSD_ERR_CAPACITY      (-7)
 
 #define GPCSD_PRED_CSD  1
@@ -597,6 +600,31 @@ int gpcsd_masked_gram(gpcsd_ctx *ctx, const double *Qs, int nx, const double *Qt
  * of auditory_lfp/fit_mean_function.py:311-321 (alpha = Qs^T resid Qt; quad = -0.5 * sum(alpha^2 / Dvec)). */
 int gpcsd_whitened_quad(gpcsd_ctx *ctx, const double *Qs, int nx, const double *Qt, int nt, const double *Dvec,
                         const double *resid, int nb, double *out);
+
+/* The trial-shift objective of auditory_lfp/fit_mean_function.py:306-321 and its analytic gradient, with everything resident: a PLAN
+ * (this call) uploads once the decomposition (Qs, Qt, Dvec of gpcsd_eig_D, Dvec taken as given), the trials lfp (nx, nt, ntrials), the
+ * means mu (nx, nt, nseg + 1) -- background in [..., 0], component i in [..., i + 1] -- and the strictly increasing time grid t (nt),
+ * which need not be uniform; it stores the trials as (x, trial, t) and forms the slope tables s_i[x][k] = (y_i[x][k+1] - y_i[x][k]) /
+ * (t[k+1] - t[k]).  One plan per context, in the named buffers "shift_*"; a new plan replaces it.  rc -3: NULL inputs, an empty
+ * shape, nt < 2, or a t that is not finite and strictly increasing (the previous plan stays); GPCSD_ERR_CAPACITY (before anything is
+ * read): nseg > GPCSD_MAX_SHIFT_NSEG, nx > 65535, nt >= 2^22. */
+int gpcsd_shift_plan(gpcsd_ctx *ctx, const double *Qs, int nx, const double *Qt, int nt, const double *Dvec, const double *lfp,
+                     int ntrials, const double *mu, int nseg, const double *t);
+/* B points (trial_idx[b], tau[b][0..nseg)) of the plan's objective (auditory_lfp/fit_mean_function.py:306-321) in one batch:
+ *   mean[x][k] = mu_0[x][k] + sum_i y_i[x][lo] + s_i[x][lo] ((t_k + tau_i) - t_lo),  lo = clip(searchsorted_left(t, t_k + tau_i), 1, nt-1) - 1
+ *   (scipy.interpolate.interp1d, linear, fill_value="extrapolate": a sample on a knot takes the segment to its left, samples outside
+ *   the grid extend the end segments),  r = lfp[:, :, trial] - mean,  alpha = Qs^T r Qt,  beta = alpha / Dvec,  Z = Qs beta Qt^T,
+ *   f_out[b] = 1/2 sum alpha beta + 1/2 sum_i ((tau_i - mutau) / sigtau)^2,
+ *   g_out[b][i] = -sum_{x,k} Z[x][k] s_i[x][lo(i,k)] + (tau_i - mutau) / sigtau^2   (the derivative on the segments in use: the LEFT
+ *   derivative where a sample sits on a knot, tau = 0 included).
+ * Only trial_idx, tau, f_out and g_out cross PCIe.  g_out may be NULL: the back-projection and the gradient kernel are then skipped
+ * and f_out has the same bits.  Fixed summation order, no atomics: the same call gives the same bits, and the kernels of this path do
+ * not see which other points share the batch (the four products are the library's GEMM, whose tile configuration follows the batch's
+ * size).  rc -2: no plan; rc -3 (nothing is launched): NULL inputs, B < 1, a trial index outside [0, ntrials), a tau that is
+ * not finite, sigtau <= 0; GPCSD_ERR_CAPACITY (nothing is launched): B * nt >= GPCSD_MAX_GEMM_LD_KMAJOR, nx * B or B * nseg * nt >=
+ * 2^31 -- evaluate in chunks of B, as the Python layer does. */
+int gpcsd_shift_eval(gpcsd_ctx *ctx, const int *trial_idx, const double *tau, int B, double mutau, double sigtau, double *f_out,
+                     double *g_out);
 
 /* Precision of the Gram builders (temporal SE / Matern, spatial SE, forward-model weights; covariances.py:50-96,177-232,
  * 257-305): bits = 64 (default) evaluates them exactly as the reference does; bits = 32 is the "fp32 kernel build + fp64
