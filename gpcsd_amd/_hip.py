@@ -171,6 +171,10 @@ SIGNATURES = {
     "gpcsd_predict_var": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _DP, _DP, _DP, _DP]),
     "gpcsd_predict_var_resident": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I]),
     "gpcsd_var_contract": (_I, [_P, _DP, _I, _I, _DP, _I, _I, _DP, _DP, _DP]),
+    "gpcsd_predict_functionals": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _DP, _I, _I] + [_DP] * 12),
+    "gpcsd_predict_functionals_resident": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _DP, _I, _I]),
+    "gpcsd_fun_gram": (_I, [_P, _DP, _I, _I, _I, _I, _DP, _DP, _I, _DP]),
+    "gpcsd_fun_gram_chunk": (_I, [_I]),
     "gpcsd_loo": (_I, [_P, ctypes.POINTER(HParams), _DP, _DP, _DP, _DP]),
     "gpcsd_loo_resident": (_I, [_P, ctypes.POINTER(HParams), _I]),
     "gpcsd_loo_contract": (_I, [_P, _DP, _DP, _DP, _DP, _I, _I, _I, _I, _DP, _DP, _DP]),
@@ -316,6 +320,12 @@ def _arr(a, shape=None, name="array"):
 
 def _ptr(a):
     return a.ctypes.data_as(_c_double_p) if a is not None else None
+
+
+def fun_gram_chunk(K):
+    """Values of b per chunk of the Gram kernel of predict_functionals (gpcsd_fun_gram_chunk): a function of the contracted row
+    length K alone.  No device call."""
+    return int(load_library().gpcsd_fun_gram_chunk(int(K)))
 
 
 class PinnedPool:
@@ -1001,6 +1011,49 @@ class Context:
         nts = P.shape[1] // C
         out = np.empty((C + 1, nz, nts))
         self._check(self._lib.gpcsd_var_contract(self._h, _ptr(G), nz, K, _ptr(P), int(C), nts, _ptr(prior_s), _ptr(kd), _ptr(out)))
+        return out
+
+    def predict_functionals(self, hp, z, tstar, W, type_code, ntrials):
+        """Posterior of linear functionals (gpcsd_predict_functionals) as host arrays: per requested quantity q the keys "q_mean"
+        (J, ntrials), "q_cov", "q_prior" (J, J) and their "_list" forms with a leading axis of the C temporal components."""
+        z = _arr(z)
+        tstar = _arr(tstar).reshape(-1)
+        W = _arr(W)
+        J, C, R = W.shape[0], hp.n_temporal, int(ntrials)
+        bufs = {}
+        for name, bit in (("csd", PRED_CSD), ("lfp", PRED_LFP)):
+            on = bool(type_code & bit)
+            for kind, shape in (("mean", (J, R)), ("cov", (J, J)), ("prior", (J, J))):
+                bufs["%s_%s_list" % (name, kind)] = np.empty((C,) + shape) if on else None
+                bufs["%s_%s" % (name, kind)] = np.empty(shape) if on else None
+        order = ["%s_%s%s" % (name, kind, suf) for name in ("csd", "lfp") for kind in ("mean", "cov", "prior") for suf in ("_list", "")]
+        self._check(self._lib.gpcsd_predict_functionals(self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size, _ptr(W), J,
+                                                        int(type_code), *[_ptr(bufs[k]) for k in order]))
+        return {k: v for k, v in bufs.items() if v is not None}
+
+    def predict_functionals_resident(self, hp, z, tstar, W, type_code):
+        """The same into the device buffers "fun_mean_csd", "fun_cov_csd", "fun_prior_csd", their "_list" forms and the "lfp" ones
+        only; read back with fetch()."""
+        z = _arr(z)
+        tstar = _arr(tstar).reshape(-1)
+        W = _arr(W)
+        self._check(self._lib.gpcsd_predict_functionals_resident(self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size,
+                                                                 _ptr(W), W.shape[0], int(type_code)))
+
+    def fun_gram(self, A, s=None, B=None):
+        """out (C + 1, J, N): out[p, j, k] = sum_{b, i} A[p, b, j, i] s[b, i] B[b, k, i], plane C with sum_p A[p] in A's place.
+        A (C, nb, J, K); s (nb, K) or None; B (nb, N, K), or None for B = A[p] (N = J; symmetric bit for bit)."""
+        A = _arr(A)
+        if A.ndim != 4:
+            raise ValueError("fun_gram: A (C, nb, J, K)")
+        C, nb, J, K = A.shape
+        s = None if s is None else _arr(s)
+        B = None if B is None else _arr(B)
+        if (s is not None and s.shape != (nb, K)) or (B is not None and (B.ndim != 3 or B.shape[0] != nb or B.shape[2] != K)):
+            raise ValueError("fun_gram: s (nb, K), B (nb, N, K)")
+        N = J if B is None else B.shape[1]
+        out = np.empty((C + 1, J, N))
+        self._check(self._lib.gpcsd_fun_gram(self._h, _ptr(A), C, nb, J, K, _ptr(s), _ptr(B), N, _ptr(out)))
         return out
 
     def loo(self, hp, shape, want_mean=True):

@@ -592,4 +592,27 @@ void k_shift_quad(gpcsd_ctx *c, const ShiftDesc &d, const double *alpha, double 
 // g[b][i] = -sum_{x,k} Z[x][b][k] slope_i[x][lo(b,i,k)] + (tau_i - mutau) / sigtau^2; part: B * shift_slabs(nx) * nseg doubles
 void k_shift_grad(gpcsd_ctx *c, const ShiftDesc &d, const double *Z, double *part, double *g, hipStream_t s);
 
+// ---------------------------------------------------------------- posterior of linear functionals (fungram.hip)
+// The long-K scaled Gram: out[p][j][k] = sum_b sum_i A_p[b][j][i] s[b][i] B[b][k][i], b < nb, i < K.  A (C, nb, J, K); plane p = C reads
+// sum_c A_c, added in registers in index order; s (nb, K) or null; B (nb, N, K), or null for B = A_p: symmetric bit for bit.
+// The range of b is cut into chunks of fun_gram_chunk(K), one partial tile per chunk in `part` (fun_gram_part_elems doubles), added
+// in chunk order by a second launch: no atomics, the same bits on every call.
+struct FunGramDesc {
+    const double *A = nullptr;
+    int C = 1, nb = 0, J = 0, K = 0;
+    const double *s = nullptr;
+    const double *B = nullptr;
+    int N = 0;
+    double *part = nullptr;
+    double *list = nullptr;         // (C, J, N)
+    double *sum = nullptr;          // (J, N): plane C
+    const char *prof_name = "fun_gram";
+};
+int fun_gram_chunk(int K);          // b per chunk: a function of the contracted row length alone
+size_t fun_gram_part_elems(int C, int nb, int J, int K, int N);
+void k_fun_gram(gpcsd_ctx *c, const FunGramDesc &d, hipStream_t s);
+void k_fun_relayout(gpcsd_ctx *c, const double *in, int J, int n1, int n2, double *out, hipStream_t s);      // (J, n1, n2) -> (n1, J, n2)
+// prior[p] = both triangles of raw[p] (J, J) from its lower one, cov[p] = prior[p] - expl[p], p < planes
+void k_fun_finish(gpcsd_ctx *c, const double *raw, const double *expl, int J, int planes, double *prior, double *cov, hipStream_t s);
+
 }  // namespace gpcsd

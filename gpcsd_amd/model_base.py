@@ -877,6 +877,79 @@ class GPCSDModel:
         self.t_var = tstar
         self.x_var = z
 
+    def predict_functionals(self, z, tstar, W, type="csd", resident=False):
+        """Posterior mean and COVARIANCE of J linear summaries <W_j, f> = sum_{z,s} W[j, z, s] f(z, tstar_s) of the CSD and/or LFP
+        field: a layer and time-window average, a sink-minus-source contrast, the amplitude of a segmented component
+        (`utility_functions.roi_weights` builds box averages and their differences).  The model is that of `predict_at` /
+        `predict_var`, which are the special case of point-mass weights: no jitter, a per-electrode noise list on the eigen-index,
+        the LFP the noise-free potential.  Exact -- no Monte-Carlo error as with `sample_posterior` draws pushed through the summary --
+        and with the posterior correlations that summing `predict_var` over a region ignores.
+
+        z, tstar, type and resident as in `predict_at` / `predict_var`; W is float64 of shape (J, nz, ntstar), J >= 1 (ValueError on
+        any other shape or on non-finite entries, before any device call).  Per requested quantity q in {csd, lfp} it sets, and
+        returns in a dict under the same names,
+
+          q_fun_mean        (J, ntrials)   posterior mean of every summary for every (local) trial, the sum of the components
+          q_fun_mean_list   C of those     per temporal component
+          q_fun_cov         (J, J)         posterior covariance of the summaries, the sum of the components -- NOT the sum of
+                                           q_fun_cov_list: the components are correlated a posteriori
+          q_fun_cov_list    C x (J, J)     per temporal component
+          q_fun_prior, q_fun_prior_list    the prior covariance of the summaries, as the cov
+
+        and `t_fun = tstar`, `x_fun = z`, `W_fun_shape`.  sqrt(diag(q_fun_cov)) is the standard error of a summary and
+        (mean_j - mean_k) / sqrt(cov_jj + cov_kk - 2 cov_jk) the z-score of a contrast.  The covariances do not depend on the trials,
+        are symmetric bit for bit and are returned UNCLAMPED (prior - explained may leave a slightly negative diagonal entry where
+        the data pin a summary down below the resolution of float64).  Every sum is formed in a fixed order: the same call gives
+        the same bits.  The attributes of the means, variances, leave-one-out scores and draws are left alone.
+
+        Under trial sharding every rank computes the same covariances locally (no communication) and the means of its own trials,
+        as in `predict_at`; `gather_predictions` does not apply.  User-defined temporal covariances are not supported (no k(t*, t*)
+        on the device): NotImplementedError.  GPCSDCapacityError when the scratch (n_components * J * nx * nt doubles and about as
+        much again) exceeds GPCSD_FUN_SCRATCH_MB megabytes (default 2048).  No reference counterpart."""
+        if type not in ("csd", "lfp", "both"):
+            raise ValueError("type must be 'csd', 'lfp' or 'both'")
+        z = np.asarray(z, dtype=np.float64)
+        z2 = z.reshape(-1, 1) if self.dim == 1 else z
+        tstar = np.asarray(tstar)
+        if tstar.size < 1:
+            raise ValueError("tstar must hold at least one time")
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        nz, nts = z2.shape[0], tstar.size
+        if W.ndim != 3 or W.shape[0] < 1 or W.shape[1:] != (nz, nts):
+            raise ValueError("predict_functionals: W must have shape (J, nz, ntstar) = (J >= 1, %d, %d), not %s" % (nz, nts, W.shape))
+        if not np.all(np.isfinite(W)):
+            raise ValueError("predict_functionals: W holds non-finite entries")
+        if self._uses_host_kt():
+            raise NotImplementedError("predict_functionals: a user-defined temporal covariance has no prior covariance k(t*, t*) on the "
+                                      "device; only GPCSDTemporalCovSE / GPCSDTemporalCovMatern components are supported")
+        ctx = self._sync_device()
+        hp, _keep = self._hparams(0.0)                     # no jitter, as predict
+        code = {"csd": _hip.PRED_CSD, "lfp": _hip.PRED_LFP, "both": _hip.PRED_BOTH}[type]
+        J, C, R_local = W.shape[0], len(self.temporal_cov_list), self._local_lfp().shape[2]
+        if resident:
+            ctx.predict_functionals_resident(hp, z2, tstar, W, code)
+            raw = {}
+            for name, bit in (("csd", _hip.PRED_CSD), ("lfp", _hip.PRED_LFP)):
+                if code & bit:
+                    for kind, shape in (("mean", (J, R_local)), ("cov", (J, J)), ("prior", (J, J))):
+                        raw["%s_%s" % (name, kind)] = ctx.device_array("fun_%s_%s" % (kind, name), shape)
+                        raw["%s_%s_list" % (name, kind)] = ctx.device_array("fun_%s_%s_list" % (kind, name), (C,) + shape)
+        else:
+            raw = ctx.predict_functionals(hp, z2, tstar, W, code, R_local)
+        res = {}
+        for name in ("csd", "lfp"):
+            for kind in ("mean", "cov", "prior"):
+                key = "%s_%s" % (name, kind)
+                if raw.get(key) is not None:
+                    res["%s_fun_%s" % (name, kind)] = raw[key]
+                    res["%s_fun_%s_list" % (name, kind)] = [raw[key + "_list"][i] for i in range(C)]
+        for k, v in res.items():
+            setattr(self, k, v)
+        self.t_fun = tstar
+        self.x_fun = z
+        self.W_fun_shape = tuple(W.shape)
+        return res
+
     def loo(self, mean=True, resident=False):
         """Leave-one-out cross-validation of the model under its current hyper-parameters, in closed form and without a refit
         (Rasmussen & Williams, Gaussian Processes for Machine Learning, 5.4.2): how well the fitted model explains the recording

@@ -7,7 +7,8 @@ the band-pass + Hilbert + phase-locking step the reference's analysis scripts en
 launches (csrc/phase.hip); torus_graph, the conditional phase coupling those scripts fit next, likewise (csrc/torus.hip);
 spectral_operator, power_spectrum, cross_spectrum, spectrum_from_sums: the periodogram those scripts take of every prediction, its
 mean over the trials and the coherence of all site pairs (csrc/spectrum.hip); trial_shift_objective: the objective of the per-trial
-shift fits those scripts run (auditory_lfp/fit_mean_function.py:306-321) with its analytic gradient (csrc/shift.hip)."""
+shift fits those scripts run (auditory_lfp/fit_mean_function.py:306-321) with its analytic gradient (csrc/shift.hip);
+roi_weights: box averages and contrasts over (z, t*) as the dense weights of predict_functionals (host only)."""
 import numpy as np
 
 from . import _hip
@@ -500,3 +501,38 @@ def fit_trial_shifts(evec_s, evec_t, Dvec, lfp_trials, mu_lfp, t, tau0=None, mut
     tau_hat = np.array([out[i].x for i in range(ntrials)])
     res = (tau_hat, np.array([bool(out[i].success) for i in range(ntrials)]), [out[i].message for i in range(ntrials)])
     return res + ({"batches": _ev.batches, "points": _ev.points},) if return_evals else res
+
+
+def roi_weights(z, tstar, site_sets, time_windows, contrast=None):
+    """Dense weights W (J, nz, ntstar) for `predict_functionals`: region-of-interest AVERAGES of a field over (z, tstar), and
+    differences of two of them.  Plain NumPy, no device call.
+
+    Box b is the sites `site_sets[b]` -- indices into the rows of z, or a boolean mask of length nz -- times the times of tstar inside
+    the closed window `time_windows[b] = (t_lo, t_hi)`; its weight is 1 / (sites x times in the box) on the box and 0 elsewhere, so
+    <W_b, f> is the mean of f over the box.  `site_sets` and `time_windows` have one entry per box.  contrast=None returns the boxes
+    themselves (J = number of boxes); contrast = [(a, b), ...] returns W[a] - W[b] per pair instead (a sink-minus-source contrast).
+    ValueError on an empty box, an index outside z or the boxes, or lists of different lengths."""
+    nz = np.asarray(z).shape[0]
+    ts = np.asarray(tstar, dtype=np.float64).reshape(-1)
+    if len(site_sets) != len(time_windows) or len(site_sets) < 1:
+        raise ValueError("roi_weights: site_sets and time_windows need one entry per box, at least one box")
+    W = np.zeros((len(site_sets), nz, ts.size))
+    for b, (sites, (lo, hi)) in enumerate(zip(site_sets, time_windows)):
+        sites = np.asarray(sites)
+        if sites.dtype == bool:
+            if sites.shape != (nz,):
+                raise ValueError("roi_weights: the mask of box %d has shape %s, not (%d,)" % (b, sites.shape, nz))
+            sites = np.flatnonzero(sites)
+        sites = np.unique(sites.astype(np.int64).reshape(-1))
+        if sites.size and (sites[0] < 0 or sites[-1] >= nz):
+            raise ValueError("roi_weights: box %d names a site outside [0, %d)" % (b, nz))
+        times = np.flatnonzero((ts >= lo) & (ts <= hi))
+        if sites.size == 0 or times.size == 0:
+            raise ValueError("roi_weights: box %d is empty (%d sites, %d times)" % (b, sites.size, times.size))
+        W[np.ix_([b], sites, times)] = 1.0 / (sites.size * times.size)
+    if contrast is None:
+        return W
+    pairs = np.asarray(contrast, dtype=np.int64).reshape(-1, 2)
+    if pairs.size == 0 or pairs.min() < 0 or pairs.max() >= W.shape[0]:
+        raise ValueError("roi_weights: contrast needs pairs (a, b) of box indices below %d" % W.shape[0])
+    return np.ascontiguousarray(W[pairs[:, 0]] - W[pairs[:, 1]])

@@ -556,6 +556,45 @@ int gpcsd_sample_posterior(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double
 int gpcsd_sample_posterior_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double *z, int nz,
                                     const double *tstar, int ntstar, int type, int nsamples, unsigned long long seed,
                                     const double *normals_xi, const double *normals_eps);
+/* Posterior mean and covariance of J LINEAR FUNCTIONALS <W_j, f> = sum_{z,s} W_j[z, s] f(z, t*_s) of the CSD / LFP field at the sites
+ * z and times tstar of gpcsd_predict_at -- a layer and window average, a sink-minus-source contrast, a component's amplitude -- of the
+ * model whose mean that call returns (no jitter; a per-electrode noise list on the eigen-index; the LFP is the noise-free potential).
+ * NO REFERENCE COUNTERPART.  W (J, nz, ntstar), C order.  With alpha_j^c = (Qs (x) Qt)^T (Kcross (x) k_c(t, t*)) vec(W_j), one
+ * (nx, nt) array per functional and temporal component c, and alpha_j^C = sum_c alpha_j^c for the component sum (plane p = C),
+ *   mean_p[j, r]  = <alpha_j^p, (Qs^T y_r Qt) / D>
+ *   prior_p[j, k] = <W_j, Kzz W_k Ktt_p>,     Kzz the prior spatial covariance at the sites, Ktt_p = k_p(t*, t*), Ktt_C = sum_c Ktt_c
+ *   cov_p[j, k]   = prior_p[j, k] - <alpha_j^p, alpha_k^p / D>       (plane C is NOT sum_c cov_c: the components are correlated a
+ *                                                                      posteriori)
+ * gpcsd_predict_var / gpcsd_predict_at are the special case of point-mass weights.  The covariances are returned UNCLAMPED, are
+ * symmetric bit for bit, and read no trial data.  Outputs per quantity (any may be NULL): *_mean_list (n_temporal, J, ntrials),
+ * *_mean (J, ntrials), *_cov_list / *_prior_list (n_temporal, J, J), *_cov / *_prior (J, J).  Every sum is formed in a fixed order:
+ * the same call returns the same bits.  The scratch -- alpha is n_temporal * J * nx * nt doubles -- is bounded by
+ * GPCSD_FUN_SCRATCH_MB megabytes (default 2048; read per call; J = 64 at 384 x 500 with two components, z = x and t* = t needs about 810):
+ * GPCSD_ERR_CAPACITY beyond it, or when J > 65535 or a row of J * nt, J * ntstar, ntrials * nt or n_temporal * ntstar doubles
+ * reaches 2^22, before z, tstar or W is read.  rc -3: bad arguments, a user-defined temporal covariance (GPCSD_KIND_HOST: no
+ * k_c(t*, t*) on the device); rc -4 without resident data. */
+int gpcsd_predict_functionals(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double *z, int nz,
+                              const double *tstar, int ntstar, const double *W, int J, int type,
+                              double *csd_mean_list, double *csd_mean, double *csd_cov_list, double *csd_cov,
+                              double *csd_prior_list, double *csd_prior,
+                              double *lfp_mean_list, double *lfp_mean, double *lfp_cov_list, double *lfp_cov,
+                              double *lfp_prior_list, double *lfp_prior);
+/* Same computation (no reference counterpart), results left in the named device buffers "fun_mean_csd" (J*ntrials), "fun_cov_csd",
+ * "fun_prior_csd" (J*J), their "_list" forms (n_temporal times that) and the "lfp" ones for gpcsd_fetch / gpcsd_device_buffer.  Waits
+ * for its own work: a numerical failure (rc > 0) is returned by the call itself.  The buffers of the posterior means, variances,
+ * leave-one-out scores and draws are left alone. */
+int gpcsd_predict_functionals_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double *z, int nz,
+                                       const double *tstar, int ntstar, const double *W, int J, int type);
+/* The Gram kernel of gpcsd_predict_functionals alone, on host arrays (no reference counterpart; fungram.hip: upload, two launches,
+ * download): A (C, nb, J, K), s (nb, K) or NULL, B (nb, N, K) or NULL -> out (C + 1, J, N), N = J when B is NULL,
+ *   out[p][j][k] = sum_b sum_i A_p[b][j][i] s[b][i] B[b][k][i],      A_C = sum_c A_c (added in index order, never stored).
+ * B NULL: B = A_p, and out[p] is symmetric bit for bit.  The range of b is cut into chunks of gpcsd_fun_gram_chunk(K) whose
+ * partial products are added in chunk order: the same call returns the same bits.  rc -3: bad arguments, C outside
+ * [1, GPCSD_MAX_TEMPORAL]; GPCSD_ERR_CAPACITY: more than 65535 chunks. */
+int gpcsd_fun_gram(gpcsd_ctx *ctx, const double *A, int C, int nb, int J, int K, const double *s, const double *B, int N,
+                   double *out);
+/* Values of b per chunk of gpcsd_fun_gram: a function of the contracted row length K alone (-3 for K < 1). */
+int gpcsd_fun_gram_chunk(int K);
 
 /* Posterior means with MISSING SAMPLES: gpcsd_predict_at of the model conditioned on the observed samples only.  NO REFERENCE
  * COUNTERPART: the reference needs the full (electrode, time, trial) grid.  mask: bytes in the data's layout (nx, nt, mask_trials),
