@@ -177,6 +177,9 @@ SIGNATURES = {
     "gpcsd_fun_gram_chunk": (_I, [_I]),
     "gpcsd_loo": (_I, [_P, ctypes.POINTER(HParams), _DP, _DP, _DP, _DP]),
     "gpcsd_loo_resident": (_I, [_P, ctypes.POINTER(HParams), _I]),
+    "gpcsd_fisher": (_I, [_P, ctypes.POINTER(HParams), _DP, _I]),
+    "gpcsd_trial_scores": (_I, [_P, ctypes.POINTER(HParams), _DP, _I]),
+    "gpcsd_trial_scores_resident": (_I, [_P, ctypes.POINTER(HParams), _I]),
     "gpcsd_loo_contract": (_I, [_P, _DP, _DP, _DP, _DP, _I, _I, _I, _I, _DP, _DP, _DP]),
     "gpcsd_analytic": (_I, [_P, _DP, _I, _I, _L, _DP, _DP, _I, _DP, _DP, _DP, _DP]),
     "gpcsd_analytic_resident": (_I, [_P, ctypes.c_char_p, _L, _I, _I, _L, _DP, _DP, _I, _I]),
@@ -1068,6 +1071,23 @@ class Context:
     def loo_resident(self, hp, want_mean=True):
         """The same into the device buffers "loo_var", "loo_lpd", "loo_sse" (and "loo_mean") only; read back with fetch()."""
         self._check(self._lib.gpcsd_loo_resident(self._h, ctypes.byref(hp), int(bool(want_mean))))
+
+    # ---- hyper-parameter uncertainty (fisher.hip, capi_fisher.inl) ----
+    def fisher(self, hp, ng):
+        """Expected Fisher information of ONE trial in natural parameters (gpcsd_fisher): (ng, ng), symmetric bit for bit."""
+        info = np.empty((int(ng), int(ng)))
+        self._check(self._lib.gpcsd_fisher(self._h, ctypes.byref(hp), _ptr(info), int(ng)))
+        return info
+
+    def trial_scores(self, hp, ntrials, ng):
+        """Per-trial scores d log p(y_r) / d theta_i of the resident trials (gpcsd_trial_scores): (ntrials, ng)."""
+        scores = np.empty((int(ntrials), int(ng)))
+        self._check(self._lib.gpcsd_trial_scores(self._h, ctypes.byref(hp), _ptr(scores), int(ng)))
+        return scores
+
+    def trial_scores_resident(self, hp, ng):
+        """The same into the device buffer "trial_scores" only; read back with fetch()."""
+        self._check(self._lib.gpcsd_trial_scores_resident(self._h, ctypes.byref(hp), int(ng)))
 
     def loo_contract(self, V, Qt, c, Y, R, want_mean=True):
         """The last product of loo() alone (gpcsd_loo_contract): V (nx * R, K), Qt (nt, K), c (nx, nt), Y (nx * R, nt) ->

@@ -696,12 +696,13 @@ static bool two_stream_front() {            // GPCSD_TWO_STREAM=0: single batche
 // join_s = false: the caller calls join_spatial() itself.  Fold views (fold_mode) must be taken AFTER this returns.
 // want_tri: the caller's tail works from the temporal tridiagonalisation + Q alone (EigState::tri tells it whether it may).
 // x_via_tri_pre: ... and forms X = Y~ Q through loglik_tri_pre, where a pipelined stage 5 is queued (TChain).
+// need_lfp = false: the caller reads no trial data (gpcsd_fisher) and has set the context's shapes itself when none is resident.
 // merged_s: the spatial side's merged spectrum and eigenvectors are wanted although the temporal side's are not (-1: as need_merged).
 EigState front_half(gpcsd_ctx *c, const gpcsd_hparams *hp, double jitter, bool need_merged = true, bool join_s = true,
-                    bool want_tri = false, int merged_s = -1, bool x_via_tri_pre = false) {
+                    bool want_tri = false, int merged_s = -1, bool x_via_tri_pre = false, bool need_lfp = true) {
     const bool need_merged_s = merged_s < 0 ? need_merged : merged_s != 0;
     const Geo g = resident_geo(c);
-    GP_REQUIRE(c->d_lfp != nullptr, -4, "lfp not set (call gpcsd_set_lfp)");
+    GP_REQUIRE(c->d_lfp != nullptr || !need_lfp, -4, "lfp not set (call gpcsd_set_lfp)");
     GP_REQUIRE(c->time_nt == c->nt, -4, "time grid has %d points but lfp has nt=%d", c->time_nt, c->nt);
     GP_REQUIRE(g.nx == c->nx, -4, "geometry has %d electrodes but lfp has nx=%d", g.nx, c->nx);
     check_hp(c, hp, c->nx);
@@ -1419,5 +1420,6 @@ extern "C" int gpcsd_set_time(gpcsd_ctx *c, const double *t, int nt) {
 #include "capi_shift.inl"
 #include "capi_torus.inl"
 #include "capi_grad.inl"
+#include "capi_fisher.inl"
 #include "capi_measure.inl"
 #include "capi_dist.inl"

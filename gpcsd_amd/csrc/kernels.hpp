@@ -615,4 +615,40 @@ void k_fun_relayout(gpcsd_ctx *c, const double *in, int J, int n1, int n2, doubl
 // prior[p] = both triangles of raw[p] (J, J) from its lower one, cov[p] = prior[p] - expl[p], p < planes
 void k_fun_finish(gpcsd_ctx *c, const double *raw, const double *expl, int J, int planes, double *prior, double *cov, hipStream_t s);
 
+// ---------------------------------------------------------------- hyper-parameter uncertainty (fisher.hip)
+// The score product: quad[b][r] = sum over the entries (m, n) of trial r of (A_b B_b)[m][n] E[m][n] w[.], b < batch, with no C
+// stored.  trial_in_col: N = R nt, the trial is n / nt and w = w[n % nt] (Ahat_p B); else M = nx R, the trial is m % R and
+// w = w[m / R] (B Bhat_q).  Per-tile partial sums per column (row), added per trial in index order by a second launch: no
+// atomics, and a trial's sum does not depend on R.
+struct FisherScoreDesc {
+    const double *A = nullptr;      // (M, K) row-major, batch entries sA apart
+    long lda = 0, sA = 0;
+    const double *B = nullptr;      // (K, N) row-major, batch entries sB apart
+    long ldb = 0, sB = 0;
+    const double *E = nullptr;      // (M, N) row-major
+    long lde = 0;
+    const double *w = nullptr;
+    int M = 0, N = 0, K = 0, batch = 1;
+    bool trial_in_col = true;
+    int nt = 0, R = 0;
+    double *quad = nullptr;         // (batch, R)
+    const char *prof_name = "fisher_score";
+};
+void k_fisher_score(gpcsd_ctx *c, const FisherScoreDesc &d, hipStream_t s);
+void k_fisher_trial_sumsq(gpcsd_ctx *c, const double *B, int nx, int R, int nt, double *quad, hipStream_t s);     // quad[r] = |B_r|^2, B [x][r][t]
+// scores[r][i] = 1/2 quad[i][r] - 1/2 trace[i]
+void k_fisher_scores(gpcsd_ctx *c, const double *quad, const double *trace, int R, int ng, double *scores, hipStream_t s);
+// out[pair(a <= b)] = sum_e X_a[e] X_b[e] W[e] over nm matrices of n2 elements, pairs in the order (0,0), (0,1), .., (1,1), ..
+void k_fisher_pairs(gpcsd_ctx *c, const double *X, const double *W, long n2, int nm, double *out, hipStream_t s);
+// out[i] = sum sv_i[x] tv_i[t] U[x][t] (i < ng); out[ng + pair(i <= j)] = sum sv_i sv_j tv_i tv_j U^2; sv (ng, nx), tv (ng, nt)
+void k_fisher_diag(gpcsd_ctx *c, const double *sv, const double *tv, const double *U, int nx, int nt, int ng, double *out, hipStream_t s);
+// sv / tv of the nsp spatial directions (diag Ahat_p, et), the ntp temporal ones (es, diag Bhat_q) and the noise (1, 1); es2, et2
+void k_fisher_weights(gpcsd_ctx *c, const double *Ah, const double *Bh, const double *es, const double *et, int nx, int nt, int nsp,
+                      int ntp, double *sv, double *tv, double *es2, double *et2, hipStream_t s);
+// dA/dR (nx, G) as a matrix (ngl2 == 0: 1D)
+void k_fisher_dA_dR(gpcsd_ctx *c, const double *x, int nx, const double *gx1, const double *gw1, const double *gx2, const double *gw2,
+                    int G, int ngl2, double R, double eps, double *out, hipStream_t s);
+// out[2c] = dKt / d ell_c, out[2c + 1] = dKt / d sigma2_c, (nt, nt) each
+void k_fisher_temporal_dgram(gpcsd_ctx *c, const TemporalSet &set, const double *t, int nt, double *out, hipStream_t s);
+
 }  // namespace gpcsd

@@ -991,6 +991,110 @@ class GPCSDModel:
             total = float(sh.allreduce_sum(np.array([total]))[0])
         return total
 
+    # ------------------------------------------------------------------ hyper-parameter uncertainty
+    def _fisher_args(self, who):
+        """(ctx, hp, keep, ng) of the score / information calls: the model of loglik(), scalar noise only."""
+        if not self._sig2n_is_scalar():
+            raise NotImplementedError("%s: a per-electrode noise list ties the noise to the eigen-index of Ks, so the model is not a "
+                                      "function of Ks alone; only a scalar sig2n is supported" % who)
+        host = self._uses_host_kt()
+        if host and not self._host_kt_is_differentiable():
+            raise NotImplementedError("%s: user-defined temporal covariances need compute_dKt(name)" % who)
+        ctx = self._sync_device()
+        hp, keep = self._hparams(self.JITTER, want_dkt=host)
+        return ctx, hp, keep, 1 + self.dim + 2 * len(self.temporal_cov_list) + 1
+
+    def hyperparameter_names(self):
+        """Names of the hyper-parameters in slot order: R, the spatial length scales, (ell, sigma2) per temporal component, sig2n."""
+        names = ["R"] + ["spatial_%s" % n for n in self._spatial_names]
+        for i in range(len(self.temporal_cov_list)):
+            names += ["temporal%d_ell" % (i + 1), "temporal%d_sigma2" % (i + 1)]
+        return names + ["sig2n"]
+
+    def _natural_values(self):
+        return np.array([getter() for getter, _, _, _, _ in self._param_slots()] + [self.sig2n["value"]], dtype=np.float64)
+
+    def trial_scores(self, resident=False):
+        """Per-trial scores s[r, i] = d log p(y_r | theta) / d theta_i at the current hyper-parameters, (ntrials, ng), in NATURAL
+        parameters in slot order (`hyperparameter_names()`): [R, ell_s.., (ell_t, sigma2_t).., sig2n].  Their sum over the trials is
+        the gradient that fit() follows; a trial whose row is large pulls the fit.  The sums are formed in a fixed order: the same
+        call gives the same bits, and a trial's row does not depend on which other trials are resident.  Sets `trial_scores_`.
+        resident=True: a zero-copy device view as in `predict` (this rank's block under trial sharding); otherwise a host array,
+        under `shard_trials` the blocks of all ranks gathered in trial order.  A per-electrode noise list raises
+        NotImplementedError.  No reference counterpart."""
+        ctx, hp, _keep, ng = self._fisher_args("trial_scores")
+        R_local = self._local_lfp().shape[2]
+        if resident:
+            ctx.trial_scores_resident(hp, ng)
+            self.trial_scores_ = ctx.device_array("trial_scores", (R_local, ng))
+            return self.trial_scores_
+        S = ctx.trial_scores(hp, R_local, ng)
+        sh = getattr(self, "_sharding", None)
+        if sh is not None:
+            # every rank's block at its own rows of a zero array: the sum over the ranks is the gather, in trial order
+            full = np.zeros((np.shape(self.lfp)[2], ng))
+            full[sh.local_slice(full.shape[0])] = S
+            S = sh.allreduce_sum(full.ravel()).reshape(full.shape)
+        self.trial_scores_ = S
+        return S
+
+    def fisher_information(self, kind="expected", log_params=True, fix_R=False):
+        """Fisher information of the hyper-parameters from ALL trials, (ng, ng) in slot order (`hyperparameter_names()`).
+
+          kind="expected"   R_total * I, I_ij = 1/2 tr(K^-1 d_i K K^-1 d_j K) of one trial: reads no data, no communication
+          kind="empirical"  S^T S of the per-trial scores (`trial_scores()`)
+
+        log_params=True: in the log-parameters of fit() (d/d tau = v d/d v, so I_tau = diag(v) I diag(v)); False: natural
+        parameters.  fix_R drops row and column 0.  Symmetric bit for bit.  No reference counterpart."""
+        if kind not in ("expected", "empirical"):
+            raise ValueError("kind must be 'expected' or 'empirical'")
+        if kind == "expected":
+            ctx, hp, _keep, ng = self._fisher_args("fisher_information")
+            info = ctx.fisher(hp, ng) * float(np.shape(self.lfp)[2])
+        else:
+            S = np.asarray(self.trial_scores())
+            info = S.T @ S
+            info = 0.5 * (info + info.T)
+        if log_params:
+            v = self._natural_values()
+            info = info * np.outer(v, v)                  # (one product per entry: symmetric in, symmetric out)
+        return info[1:, 1:] if fix_R else info
+
+    def hyperparameter_cov(self, kind="expected", fix_R=False):
+        """Large-sample covariance of the fitted hyper-parameters in the log-parameters of fit(), at the current values (meant for
+        the point fit() returned).  With H = I_tau - d^2(log prior) / d tau^2 (I_tau the expected information of all trials,
+        d^2/d tau^2 = v^2 lp''(v) + v lp'(v) per parameter):
+
+          kind="expected"   H^-1
+          kind="sandwich"   H^-1 (S_tau^T S_tau) H^-1, S_tau the per-trial scores in log-parameters (robust to misspecification)
+
+        Returns a dict: "names" (slot order), "cov" (log units), "se" (standard errors, log units), "value" (natural units) and
+        "interval" (n, 2) = exp(tau -+ 1.96 se) in natural units.  fix_R leaves R out.  Raises numpy.linalg.LinAlgError when H is
+        not positive definite (the point is no maximum of the posterior, or a parameter is not identified)."""
+        if kind not in ("expected", "sandwich"):
+            raise ValueError("kind must be 'expected' or 'sandwich'")
+        H = np.array(self.fisher_information("expected", log_params=True, fix_R=False))
+        v = self._natural_values()
+        priors = [prior for _, _, prior, _, _ in self._param_slots()] + [self.sig2n["prior"]]
+        for i, (pr, x) in enumerate(zip(priors, v)):
+            H[i, i] -= x * x * pr.d2lpdf(x) + x * pr.dlpdf(x)
+        names = self.hyperparameter_names()
+        if fix_R:
+            H, v, names = H[1:, 1:], v[1:], names[1:]
+        L = np.linalg.cholesky(H)                        # LinAlgError when H is not positive definite
+        Linv = np.linalg.solve(L, np.eye(H.shape[0]))
+        cov = Linv.T @ Linv
+        if kind == "sandwich":
+            S = np.asarray(self.trial_scores()) * self._natural_values()[None, :]
+            S = S[:, 1:] if fix_R else S
+            J = S.T @ S
+            cov = cov @ (0.5 * (J + J.T)) @ cov
+        cov = 0.5 * (cov + cov.T)
+        se = np.sqrt(np.diag(cov))
+        tau = np.log(v)
+        return {"names": names, "cov": cov, "se": se, "value": v,
+                "interval": np.stack([np.exp(tau - 1.96 * se), np.exp(tau + 1.96 * se)], axis=1)}
+
     @staticmethod
     def _types(type):
         if type not in ("csd", "lfp", "both"):

@@ -3,7 +3,8 @@
 Mirrors src/gpcsd/priors.py of the reference: `GPCSDInvGammaPrior` (lpdf :23-28, set_params :30-32,
 sample :34-35) and `GPCSDHalfNormalPrior` (lpdf :46-51, sample :53-54).  `dlpdf` (derivative of lpdf) is an
 addition used by the analytic gradient that replaces the reference's autograd tape; `lpdf_many` / `dlpdf_many` are the same
-expressions on arrays (all restarts of a lock-step fit at once).
+expressions on arrays (all restarts of a lock-step fit at once).  `d2lpdf` (second derivative) is the prior's curvature in
+`GPCSDModel.hyperparameter_cov`.
 """
 import numpy as np
 from scipy import stats as _stats
@@ -16,6 +17,9 @@ class GPCSDPrior:
         raise NotImplementedError
 
     def dlpdf(self, x):
+        raise NotImplementedError
+
+    def d2lpdf(self, x):
         raise NotImplementedError
 
     def sample(self):
@@ -40,6 +44,9 @@ class GPCSDInvGammaPrior(GPCSDPrior):
 
     def dlpdf(self, x):
         return -(self.alpha + 1.0) / x + self.beta / (x * x)
+
+    def d2lpdf(self, x):
+        return (self.alpha + 1.0) / (x * x) - 2.0 * self.beta / (x * x * x)
 
     # the same two expressions elementwise on an array of values (the lock-step fit evaluates all restarts' priors at once)
     def lpdf_many(self, x):
@@ -79,6 +86,9 @@ class GPCSDHalfNormalPrior(GPCSDPrior):
 
     def dlpdf(self, x):
         return -x / (self.sd * self.sd)
+
+    def d2lpdf(self, x):
+        return -1.0 / (self.sd * self.sd)
 
     def lpdf_many(self, x):
         x = np.asarray(x, dtype=np.float64)

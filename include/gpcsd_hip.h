@@ -375,6 +375,24 @@ int gpcsd_loo(gpcsd_ctx *ctx, const gpcsd_hparams *hp, double *var, double *mean
  * (nx*ntrials each) and, when want_mean != 0, "loo_mean" (nx*nt*ntrials) for gpcsd_fetch / gpcsd_device_buffer.  Waits for its own
  * work: a numerical failure (rc > 0) is returned by the call itself.  The buffers of the predictions are left alone. */
 int gpcsd_loo_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, int want_mean);
+/* Hyper-parameter uncertainty.  NO REFERENCE COUNTERPART: fit() (gpcsd1d.py:193-220, gpcsd2d.py:232-259) returns a point estimate
+ * and stops; tr(K^-1 d_i K K^-1 d_j K) on the (nx nt)^2 covariance is out of its reach.  Extends gpcsd_loglik_grad: the same model
+ * (Ks + hp->jitter I, a user-defined temporal Gram with its derivative matrices from gpcsd_set_host_temporal_dgram allowed), the
+ * same NATURAL parameters in the same order, ng = 1 + dim + 2 n_temporal + 1: [R, ell_s (dim), (ell_t, sigma2_t) per component,
+ * sig2n].  Scalar sig2n only: a per-electrode list (n_sig2n == nx) ties the noise to the eigen-index of Ks
+ * (utility_functions.py:54-63), so that model is not a function of Ks alone -- rc -3.
+ *   gpcsd_fisher        info (ng, ng): the expected Fisher information of ONE trial, I_ij = 1/2 tr(K^-1 d_i K K^-1 d_j K), symmetric bit
+ *                       for bit.  Reads no trial data and needs none resident (geometry and time grid only).
+ *   gpcsd_trial_scores  scores (ntrials, ng): s[r][i] = d log p(y_r) / d theta_i = 1/2 y_r^T K^-1 d_i K K^-1 y_r - 1/2 tr(K^-1 d_i K) of
+ *                       the resident trials; their sum over r is the gradient of gpcsd_loglik_grad.  rc -4 without resident data.
+ * All sums are formed in a fixed order without atomics: the same call returns the same bits, and a trial's scores do not depend on
+ * which other trials are resident.  rc -3: bad ng, a noise list, a GPCSD_KIND_HOST component without its derivative matrices;
+ * rc > 0: numerical failure of an eigensolver; GPCSD_ERR_CAPACITY as gpcsd_loo. */
+int gpcsd_fisher(gpcsd_ctx *ctx, const gpcsd_hparams *hp, double *info, int ng);
+int gpcsd_trial_scores(gpcsd_ctx *ctx, const gpcsd_hparams *hp, double *scores, int ng);
+/* Same computation, the scores left in the named device buffer "trial_scores" (ntrials*ng) for gpcsd_fetch / gpcsd_device_buffer.
+ * Waits for its own work: a numerical failure (rc > 0) is returned by the call itself. */
+int gpcsd_trial_scores_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, int ng);
 /* The last product of gpcsd_loo alone, on host arrays (no reference counterpart; upload, the launch and its reduce, download):
  * V (nx * R, K) and Qt (nt, K) give beta[(x, r)][t] = sum_k V[(x, r)][k] Qt[t][k], which is never stored; with c (nx, nt) > 0 and
  * Y (nx * R, nt): e = beta / c, mean[x][t][r] = Y[(x, r)][t] - e (mean may be NULL), lpd[(x, r)] = sum_t 1/2 log c - 1/2 beta e -
