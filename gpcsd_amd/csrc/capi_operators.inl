@@ -250,6 +250,17 @@ extern "C" int gpcsd_debug_sytrd(gpcsd_ctx *c, const double *A, int n, double *d
 extern "C" int gpcsd_debug_stedc(gpcsd_ctx *c, const double *d, const double *e, int n, double *w, double *Z) {
     GP_API_BEGIN(c)
     GP_REQUIRE(d && e && w && Z && n > 0, -3, "debug_stedc: bad arguments");
+    // stedc_device takes what the solver hands it, the tridiagonal of A / max|a| (kernels.hpp): its deflation tolerance weighs the
+    // poles against entries of unit vectors.  A caller's tridiagonal is brought there by a power of two (exact) and the
+    // eigenvalues back -- without it 2^-400 T deflated everything and returned its torn diagonal (tests/test_eigh_kernels.py).
+    double top = 0.0;
+    for (int i = 0; i < n; ++i) top = std::fmax(top, std::fmax(std::fabs(d[i]), i + 1 < n ? std::fabs(e[i]) : 0.0));
+    const int ex = (top > 0.0 && std::isfinite(top)) ? -std::ilogb(top) : 0;      // max(|d|, |e|) 2^ex in [1, 2)
+    std::vector<double> hs(2 * (size_t)n, 0.0);                                   // (alive until finish_status has synchronised)
+    for (int i = 0; i < n; ++i) hs[i] = std::ldexp(d[i], ex);
+    for (int i = 0; i + 1 < n; ++i) hs[n + i] = std::ldexp(e[i], ex);
+    d = hs.data();
+    e = hs.data() + n;
     double *dd = c->upload<double>("dbg_d", d, n);
     double *de = c->buf<double>("dbg_e", n);
     GP_HIP(hipMemsetAsync(de, 0, n * sizeof(double), c->stream));
@@ -261,7 +272,9 @@ extern "C" int gpcsd_debug_stedc(gpcsd_ctx *c, const double *d, const double *e,
     stedc_device(c, dd, de, n, dw, dZ, st, c->stream, "dbg");
     c->download(w, dw, n * sizeof(double));
     c->download(Z, dZ, (size_t)n * n * sizeof(double));
-    return finish_status(c, st);
+    const int rc = finish_status(c, st);
+    for (int i = 0; i < n; ++i) w[i] = std::ldexp(w[i], -ex);
+    return rc;
     GP_API_END(c)
 }
 

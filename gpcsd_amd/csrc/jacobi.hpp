@@ -1,5 +1,6 @@
-// Two-sided cyclic Jacobi eigensolver body (device template), shared by eigh.hip (small dense problems) and
-// eigh_dc.hip (leaves of the divide-and-conquer tridiagonal solver).
+// Two-sided cyclic Jacobi eigensolver body (device template) of eigh.hip: small dense problems in LDS, any order in global
+// memory as a cross-check.  (The 8-row leaves of the divide & conquer have a register-resident solver of their own in stedc.hip,
+// which shares the helpers and constants below, not jacobi_body and not jac_cos: a leaf column takes ~30 rotations, not ~600.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +22,21 @@ __device__ __forceinline__ double jac_rsqrt(double x) {        // x in [1, 1e300
     r = r * fma(-0.5 * x * r, r, 1.5);
     r = r * fma(-0.5 * x * r, r, 1.5);
     return r;
+}
+
+// c = 1 / sqrt(1 + t^2), |t| <= 1, for the rotation (c, s = t c).  1 + t^2 is rounded in [1, 2), where the spacing is 2^-52: the small
+// angles of the late sweeps lose their t^2 there, one-sidedly (1 + t^2 -> 1 leaves c^2 + s^2 = 1 + t^2), and every rotation stretched
+// its two columns by a fraction of an ulp -- after the ~600 rotations a column of a 64-row problem takes, V^T V - I and the
+// eigenvalues were off by 130 .. 200 unit roundoffs (tests/test_eigh_kernels.py).  So the last Newton step takes its residual
+// 1 - r^2 (1 + y) with r^2 split exactly (p + pe) and y = fl(t^2) kept apart from the 1: 1 - p is exact for p in [1/2, 1].
+// What is left: y is t^2 rounded once (relative 2^-53, of either sign, and s = t c is formed with the same t), and the term pe y of
+// the residual is dropped (|pe y| <= 2^-54 y: a quarter ulp of c at |t| = 1, the sign of a rounding error, nothing at small angles).
+__device__ __forceinline__ double jac_cos(double t) {
+    const double y = t * t;
+    const double r = jac_rsqrt(y + 1.0);
+    const double p = r * r, pe = fma(r, r, -p);
+    const double e = fma(-p, y, (1.0 - p) - pe);
+    return fma(0.5 * r, e, r);
 }
 
 // pair k of round-robin step `step` over m (even) players; returns p < q
@@ -110,9 +126,9 @@ __device__ void jacobi_body(double *A, int lda, double *V, int ldv, int n, doubl
                     const double apq = A[p * lda + q];
                     if (fabs(apq) > thresh) {
                         // The rotation angle only steers convergence; what must hold to rounding is c^2 + s^2 = 1, and
-                        // s = t c with c = rsqrt(1 + t^2) gives that for any t.  So the reciprocal / root chain uses the
-                        // ~2 ulp Newton forms (15 instructions) instead of three IEEE sequences (~110): this section is
-                        // a serial dependency of every Jacobi step.
+                        // s = t c with c = 1 / sqrt(1 + t^2) gives that for any t -- as far as c is that of THIS t
+                        // (jac_cos).  So the chain up to t uses the ~2 ulp Newton forms (15 instructions) instead of three
+                        // IEEE sequences (~110): this section is a serial dependency of every Jacobi step.
                         const double app = A[p * lda + p], aqq = A[q * lda + q];
                         const double theta = (aqq - app) * jac_rcp(2.0 * apq);
                         double t;
@@ -121,7 +137,7 @@ __device__ void jacobi_body(double *A, int lda, double *V, int ldv, int n, doubl
                             const double th2 = theta * theta + 1.0;
                             t = copysign(1.0, theta) * jac_rcp(fabs(theta) + th2 * jac_rsqrt(th2));
                         }
-                        c = jac_rsqrt(t * t + 1.0);
+                        c = jac_cos(t);
                         s = t * c;
                         active = 1;
                     }

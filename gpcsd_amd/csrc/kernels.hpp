@@ -511,7 +511,9 @@ void wy_prep_device(gpcsd_ctx *c, const WyBatch &b, int nclass, hipStream_t s); 
 // columns [col0[i], col1[i]) of class i's Q that the panel just applied completes
 void wy_q_pipeline(gpcsd_ctx *c, const WyBatch &b, int nclass, hipStream_t s,
                    const std::function<void(const int *col0, const int *col1)> &chunk, bool one_launch = false);
-// stages of the large-n solver, exposed for tests / diagnostics
+// stages of the large-n solver, exposed for tests / diagnostics.  stedc_device expects the scale the solver works at -- the
+// tridiagonal of A / max|a|, largest entry of order 1: the deflation tolerance 8 eps max(|d|, |z|) (dlaed2's, behind dstedc's own
+// scaling) compares poles with entries of unit vectors, and a tridiagonal far below 1 deflates whole (gpcsd_debug_stedc scales)
 void sytrd_device(gpcsd_ctx *c, double *A, int n, double *d, double *e, double *V, double *tau, hipStream_t s);
 void stedc_device(gpcsd_ctx *c, const double *d, const double *e, int n, double *w, double *Z, int *d_status,
                   hipStream_t s, const char *tag);

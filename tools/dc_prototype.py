@@ -120,8 +120,9 @@ def secular_root(i, K, d, z2, rho, maxit=80):
     return org, mu
 
 
-def merge(d1, Q1, d2, Q2, beta):
-    """Merge two solved halves coupled by off-diagonal beta (diagonals already reduced by |beta|)."""
+def merge(d1, Q1, d2, Q2, beta, defl_scale=1.0):
+    """Merge two solved halves coupled by off-diagonal beta (diagonals already reduced by |beta|).  defl_scale multiplies the
+    deflation tolerance (1: dlaed2's; tests/test_eigh_kernels.py widens it to show what its measures see)."""
     n1, n2 = len(d1), len(d2)
     N = n1 + n2
     rho = abs(beta)
@@ -134,7 +135,7 @@ def merge(d1, Q1, d2, Q2, beta):
     rho2 = 2.0 * rho
     # merged ascending order (stable)
     perm = np.argsort(d, kind="stable")
-    tol = 8.0 * EPS * max(np.max(np.abs(d)), np.max(np.abs(z)))
+    tol = defl_scale * 8.0 * EPS * max(np.max(np.abs(d)), np.max(np.abs(z)))
     defl = np.zeros(N, dtype=bool)
     nondefl = []
     rots = []
@@ -202,7 +203,7 @@ def merge(d1, Q1, d2, Q2, beta):
     return vals[order], cols[order].T, K
 
 
-def dc_eigh_tridiag(d, e, leaf=32):
+def dc_eigh_tridiag(d, e, leaf=32, defl_scale=1.0):
     d = np.array(d, dtype=np.float64)
     e = np.array(e, dtype=np.float64)
     n = len(d)
@@ -224,7 +225,7 @@ def dc_eigh_tridiag(d, e, leaf=32):
             a, m, w1, V1 = blocks[i]
             m2, b, w2, V2 = blocks[i + 1]
             assert m == m2
-            w, V, K = merge(w1, V1, w2, V2, e[m - 1])
+            w, V, K = merge(w1, V1, w2, V2, e[m - 1], defl_scale)
             stats.append((b - a, K))
             nxt.append((a, b, w, V))
         blocks = nxt
