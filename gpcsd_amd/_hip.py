@@ -377,6 +377,22 @@ class PinnedPool:
 pinned_pool = PinnedPool()
 
 
+def _sites_times(z, tstar):
+    """Sites and times of a posterior call as the C ABI reads them: contiguous doubles, the times flat."""
+    return _arr(z), _arr(tstar).reshape(-1)
+
+
+def _sum_list_outputs(type_code, shape, C, want_lists=True):
+    """Pinned host outputs of the form "csd / lfp x sum / list": "csd", "lfp" of `shape` and "csd_list", "lfp_list" with a leading
+    axis of the C temporal components; None for a quantity type_code does not ask for (and for the lists unless want_lists)."""
+    bufs = {}
+    for name, bit in (("csd", PRED_CSD), ("lfp", PRED_LFP)):
+        on = bool(type_code & bit)
+        bufs[name] = pinned_pool.empty(tuple(shape)) if on else None
+        bufs[name + "_list"] = pinned_pool.empty((C,) + tuple(shape)) if on and want_lists else None
+    return bufs
+
+
 class DeviceArray:
     """A float64 C-contiguous view of library-owned device memory (`__cuda_array_interface__` version 3)."""
 
@@ -953,54 +969,34 @@ class Context:
     def predict(self, hp, z, tstar, type_code, shape, want_lists=True, at=False):
         """shape = (nz, ntstar, ntrials).  Returns dict of arrays for the requested type.  at=True: gpcsd_predict_at (any ntstar,
         the training axis of the cross Grams contracted) instead of gpcsd_predict."""
-        z = _arr(z)
-        tstar = _arr(tstar).reshape(-1)
+        z, tstar = _sites_times(z, tstar)
         nz, ntstar, R = shape
-        C = hp.n_temporal
-        res = {}
-        bufs = {}
-        for name, bit in (("csd", PRED_CSD), ("lfp", PRED_LFP)):
-            if type_code & bit:
-                bufs[name] = pinned_pool.empty((nz, ntstar, R))
-                bufs[name + "_list"] = pinned_pool.empty((C, nz, ntstar, R)) if want_lists else None
-            else:
-                bufs[name] = None
-                bufs[name + "_list"] = None
+        bufs = _sum_list_outputs(type_code, (nz, ntstar, R), hp.n_temporal, want_lists)
         fn = self._lib.gpcsd_predict_at if at else self._lib.gpcsd_predict
         self._check(fn(self._h, ctypes.byref(hp), _ptr(z), nz, _ptr(tstar), tstar.size, int(type_code),
                        _ptr(bufs["csd_list"]), _ptr(bufs["csd"]), _ptr(bufs["lfp_list"]), _ptr(bufs["lfp"])))
-        for k, v in bufs.items():
-            if v is not None:
-                res[k] = v
-        return res
+        return {k: v for k, v in bufs.items() if v is not None}
 
     def predict_resident(self, hp, z, tstar, type_code, want_lists=True, at=False):
         """Compute the posterior mean into device buffers only (no PCIe traffic); read back with fetch().  at=True:
         gpcsd_predict_at_resident."""
-        z = _arr(z)
-        tstar = _arr(tstar).reshape(-1)
+        z, tstar = _sites_times(z, tstar)
         fn = self._lib.gpcsd_predict_at_resident if at else self._lib.gpcsd_predict_resident
         self._check(fn(self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size, int(type_code), int(bool(want_lists))))
 
     def predict_var(self, hp, z, tstar, type_code):
         """Posterior variances (gpcsd_predict_var) as host arrays: dict with "csd" / "lfp" (nz, ntstar) and "csd_list" / "lfp_list"
         (C, nz, ntstar) for the requested type."""
-        z = _arr(z)
-        tstar = _arr(tstar).reshape(-1)
-        nz, C = z.shape[0], hp.n_temporal
-        bufs = {}
-        for name, bit in (("csd", PRED_CSD), ("lfp", PRED_LFP)):
-            on = bool(type_code & bit)
-            bufs[name] = pinned_pool.empty((nz, tstar.size)) if on else None
-            bufs[name + "_list"] = pinned_pool.empty((C, nz, tstar.size)) if on else None
+        z, tstar = _sites_times(z, tstar)
+        nz = z.shape[0]
+        bufs = _sum_list_outputs(type_code, (nz, tstar.size), hp.n_temporal)
         self._check(self._lib.gpcsd_predict_var(self._h, ctypes.byref(hp), _ptr(z), nz, _ptr(tstar), tstar.size, int(type_code),
                                                 _ptr(bufs["csd_list"]), _ptr(bufs["csd"]), _ptr(bufs["lfp_list"]), _ptr(bufs["lfp"])))
         return {k: v for k, v in bufs.items() if v is not None}
 
     def predict_var_resident(self, hp, z, tstar, type_code):
         """The same into the device buffers "pred_var_csd", "pred_var_lfp" and their "_list" forms only; read back with fetch()."""
-        z = _arr(z)
-        tstar = _arr(tstar).reshape(-1)
+        z, tstar = _sites_times(z, tstar)
         self._check(self._lib.gpcsd_predict_var_resident(self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size,
                                                          int(type_code)))
 
@@ -1019,8 +1015,7 @@ class Context:
     def predict_functionals(self, hp, z, tstar, W, type_code, ntrials):
         """Posterior of linear functionals (gpcsd_predict_functionals) as host arrays: per requested quantity q the keys "q_mean"
         (J, ntrials), "q_cov", "q_prior" (J, J) and their "_list" forms with a leading axis of the C temporal components."""
-        z = _arr(z)
-        tstar = _arr(tstar).reshape(-1)
+        z, tstar = _sites_times(z, tstar)
         W = _arr(W)
         J, C, R = W.shape[0], hp.n_temporal, int(ntrials)
         bufs = {}
@@ -1037,8 +1032,7 @@ class Context:
     def predict_functionals_resident(self, hp, z, tstar, W, type_code):
         """The same into the device buffers "fun_mean_csd", "fun_cov_csd", "fun_prior_csd", their "_list" forms and the "lfp" ones
         only; read back with fetch()."""
-        z = _arr(z)
-        tstar = _arr(tstar).reshape(-1)
+        z, tstar = _sites_times(z, tstar)
         W = _arr(W)
         self._check(self._lib.gpcsd_predict_functionals_resident(self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size,
                                                                  _ptr(W), W.shape[0], int(type_code)))
@@ -1115,16 +1109,10 @@ class Context:
 
     def predict_masked(self, hp, mask, z, tstar, type_code, shape, want_lists=True):
         """gpcsd_predict_masked: as predict(at=True) on the observed samples only.  shape = (nz, ntstar, ntrials)."""
-        z = _arr(z)
-        tstar = _arr(tstar).reshape(-1)
+        z, tstar = _sites_times(z, tstar)
         m8, mt = self._mask_bytes(mask)
         nz, ntstar, R = shape
-        C = hp.n_temporal
-        bufs = {}
-        for name, bit in (("csd", PRED_CSD), ("lfp", PRED_LFP)):
-            on = bool(type_code & bit)
-            bufs[name] = pinned_pool.empty((nz, ntstar, R)) if on else None
-            bufs[name + "_list"] = pinned_pool.empty((C, nz, ntstar, R)) if on and want_lists else None
+        bufs = _sum_list_outputs(type_code, (nz, ntstar, R), hp.n_temporal, want_lists)
         self._check(self._lib.gpcsd_predict_masked(self._h, ctypes.byref(hp), m8.ctypes.data_as(_P), mt, _ptr(z), nz, _ptr(tstar),
                                                    tstar.size, int(type_code), _ptr(bufs["csd_list"]), _ptr(bufs["csd"]),
                                                    _ptr(bufs["lfp_list"]), _ptr(bufs["lfp"])))
@@ -1132,8 +1120,7 @@ class Context:
 
     def predict_masked_resident(self, hp, mask, z, tstar, type_code, want_lists=True):
         """The same into the device buffers of predict_resident only; read back with fetch()."""
-        z = _arr(z)
-        tstar = _arr(tstar).reshape(-1)
+        z, tstar = _sites_times(z, tstar)
         m8, mt = self._mask_bytes(mask)
         self._check(self._lib.gpcsd_predict_masked_resident(self._h, ctypes.byref(hp), m8.ctypes.data_as(_P), mt, _ptr(z), z.shape[0],
                                                             _ptr(tstar), tstar.size, int(type_code), int(bool(want_lists))))
@@ -1379,8 +1366,7 @@ class Context:
         """Joint posterior draws (gpcsd_sample_posterior): dict with "csd" / "lfp" (nz, ntstar, R, nsamples) for the requested type
         -- host arrays, or with resident=True nothing (the draws stay in "post_sample_csd" / "post_sample_lfp").  xi, eps: host
         normals (R, nsamples, ns, ntt) / (R, nsamples, nx, nt), or both None for the device generator."""
-        z = _arr(z)
-        tstar = _arr(tstar).reshape(-1)
+        z, tstar = _sites_times(z, tstar)
         xi = None if xi is None else _arr(xi)
         eps = None if eps is None else _arr(eps)
         args = (self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size, int(type_code), int(nsamples), int(seed),

@@ -223,8 +223,7 @@ extern "C" int gpcsd_trial_scores(gpcsd_ctx *c, const gpcsd_hparams *hp, double 
     FisherOut o;
     const int rc = fisher_impl(c, hp, ng, true, false, o);
     if (rc != 0) return rc;
-    c->download(scores, c->bufs["trial_scores"].p, (size_t)c->ntrials * ng * sizeof(double));
-    c->sync();
+    download_outputs(c, {{scores, "trial_scores", (size_t)c->ntrials * ng}});
     return 0;
     GP_API_END(c)
 }

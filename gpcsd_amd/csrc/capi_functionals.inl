@@ -1,4 +1,4 @@
-// Part of capi.hip (included there: one translation unit, so the file-local helpers of capi.hip and capi_fused.inl are in scope) --
+// Part of capi.hip (included there: one translation unit, so the file-local helpers of capi.hip, capi_fused.inl and capi_posterior.inl are in scope) --
 // posterior mean and covariance of linear functionals of the CSD / LFP field (gpcsd_predict_functionals) and its Gram kernel alone
 // (gpcsd_fun_gram).
 
@@ -50,16 +50,14 @@ extern "C" int gpcsd_fun_gram(gpcsd_ctx *c, const double *A, int C, int nb, int 
 // explained term is its symmetric form, the prior is made symmetric bit for bit from its lower triangle (as k_sym_place treats the
 // builders' blocks, whose diagonal blocks are symmetric only to ~1e-11).  The covariances read no trial data.
 // Outputs per quantity q: fun_mean_q (J, R), fun_cov_q / fun_prior_q (J, J) and their _list forms (C times that).
-static int predict_functionals_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar,
-                                    const double *W, int J, int type) {
-    GP_REQUIRE(z && tstar && W && nz > 0 && ntstar > 0 && J > 0, -3, "predict_functionals: bad arguments");
-    GP_REQUIRE(type >= 1 && type <= 3, -3, "predict_functionals: type must be CSD(1), LFP(2) or BOTH(3)");
-    GP_REQUIRE(hp != nullptr, -3, "null hparams");
+static int predict_functionals_impl(gpcsd_ctx *c, const PredCall &q, const double *W, int J) {
+    const gpcsd_hparams *hp = q.hp;
+    const int nz = q.nz, ntstar = q.ntstar, type = q.type;
+    GP_REQUIRE(W && J > 0, -3, "predict_functionals: bad arguments");
+    posterior_request(c, "predict_functionals", q, REQ_SITES | REQ_HP);
     GP_REQUIRE(hp->n_temporal >= 1 && hp->n_temporal <= GPCSD_MAX_TEMPORAL, -3, "n_temporal=%d outside [1,%d]", hp->n_temporal,
                GPCSD_MAX_TEMPORAL);
-    GP_REQUIRE(c->d_lfp != nullptr, -4, "lfp not set (call gpcsd_set_lfp)");
-    GP_REQUIRE(!uses_host_kt(hp), -3, "predict_functionals: a user-defined temporal covariance (GPCSD_KIND_HOST) has no prior "
-               "covariance k_c(t*, t*) on the device; only the built-in kinds are supported");
+    posterior_request(c, "predict_functionals", q, REQ_LFP | REQ_NO_HOST_KT);
     const int nx = c->nx, nt = c->nt, R = c->ntrials, C = hp->n_temporal;
     // (checked before z, tstar or W is read) rows of the flat products, one batch entry per functional, and the scratch
     const long ldmax = std::max({(long)C * ntstar, (long)J * nt, (long)J * ntstar, (long)R * nt, (long)R * ntstar});
@@ -73,14 +71,12 @@ static int predict_functionals_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const
     GP_REQUIRE(need <= fun_scratch_budget(), GPCSD_ERR_CAPACITY,
                "predict_functionals: J = %d functionals need %zu MB of scratch (alpha alone n_temporal * J * nx * nt = %zu doubles), "
                "more than the budget of %zu MB (GPCSD_FUN_SCRATCH_MB)", J, need >> 20, n_alpha, fun_scratch_budget() >> 20);
-    // the scratch of the prediction calls is rewritten below: whatever an earlier queued prediction still owes is collected first
-    if (int rc = drain_async(c)) return rc;
-    EigState e = front_half(c, hp, 0.0);           // no jitter, as predict (gpcsd1d.py:258)
+    PostFront f;
+    if (int rc = posterior_front(c, q, FRONT_DRAIN | FRONT_TRIALS, f)) return rc;
+    const EigState &e = f.e;
     const Geo g = resident_geo(c);
     hipStream_t s = c->stream;
-    const PredFullFront f = predict_full_front(c, hp, e, z, nz, tstar, ntstar, type);
-    double *Pc = pred_at_Pc(c, e, f.Kts, C, ntstar);
-    const double *dz = (const double *)c->bufs["pred_z"].p, *dts = (const double *)c->bufs["pred_tstar"].p;
+    const double *Pc = f.Pc, *dz = f.dz, *dts = f.dts;
     double *dW = c->upload<double>("fun_W", W, n_W);
     double *Wt = c->buf<double>("fun_Wt", n_W), *X = c->buf<double>("fun_X", n_W), *V = c->buf<double>("fun_V", (size_t)C * n_W);
     double *T = c->buf<double>("fun_T", n_T), *alpha = c->buf<double>("fun_alpha", n_alpha);
@@ -158,7 +154,7 @@ static int predict_functionals_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const
 extern "C" int gpcsd_predict_functionals_resident(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar,
                                                   int ntstar, const double *W, int J, int type) {
     GP_API_BEGIN(c)
-    return predict_functionals_impl(c, hp, z, nz, tstar, ntstar, W, J, type);
+    return predict_functionals_impl(c, pred_call(hp, z, nz, tstar, ntstar, type, true, false), W, J);
     GP_API_END(c)
 }
 
@@ -168,22 +164,22 @@ extern "C" int gpcsd_predict_functionals(gpcsd_ctx *c, const gpcsd_hparams *hp, 
                                          double *lfp_mean_list, double *lfp_mean, double *lfp_cov_list, double *lfp_cov,
                                          double *lfp_prior_list, double *lfp_prior) {
     GP_API_BEGIN(c)
-    const int rc = predict_functionals_impl(c, hp, z, nz, tstar, ntstar, W, J, type);
+    const int rc = predict_functionals_impl(c, pred_call(hp, z, nz, tstar, ntstar, type, true, false), W, J);
     if (rc < 0) return rc;
-    const size_t C = (size_t)hp->n_temporal, JJ = (size_t)J * J * sizeof(double), JR = (size_t)J * c->ntrials * sizeof(double);
+    const size_t C = (size_t)hp->n_temporal, JJ = (size_t)J * J, JR = (size_t)J * c->ntrials;
     double *const host[2][6] = {{csd_mean_list, csd_mean, csd_cov_list, csd_cov, csd_prior_list, csd_prior},
                                 {lfp_mean_list, lfp_mean, lfp_cov_list, lfp_cov, lfp_prior_list, lfp_prior}};
     static const char *const kind[3] = {"fun_mean_", "fun_cov_", "fun_prior_"};
+    std::vector<HostOut> outs;
     for (int w = 0; w < 2; ++w) {
         if (!(type & (w + 1))) continue;
-        const std::string q = w ? "lfp" : "csd";
         for (int k = 0; k < 3; ++k) {
-            const size_t bytes = k == 0 ? JR : JJ;
-            if (host[w][2 * k]) c->download(host[w][2 * k], c->bufs[kind[k] + q + "_list"].p, C * bytes);
-            if (host[w][2 * k + 1]) c->download(host[w][2 * k + 1], c->bufs[kind[k] + q].p, bytes);
+            const std::string name = std::string(kind[k]) + (w ? "lfp" : "csd");
+            outs.push_back({host[w][2 * k], name + "_list", C * (k == 0 ? JR : JJ)});
+            outs.push_back({host[w][2 * k + 1], name, k == 0 ? JR : JJ});
         }
     }
-    c->sync();
+    download_outputs(c, outs);
     return rc;
     GP_API_END(c)
 }

@@ -1,5 +1,6 @@
 // Part of capi.hip (included there: one translation unit, so the file-local helpers of capi.hip are in scope) --
 // fused hot calls on resident data: loglik (synchronous, queued), predict (folded / full-size, resident), the paired call, sample_prior.
+// (The posterior quantities at arbitrary times, which start from predict's full-size front, are capi_posterior.inl.)
 
 // ------------------------------------------------------------------------------------------------
 // fused hot calls
@@ -720,7 +721,8 @@ static bool pred_unfold_chunked(gpcsd_ctx *c, const PredCall &q, PredUnfoldDesc 
 // i.e. two small (n^3) products M1, Pc and two flat GEMMs, instead of back-projecting to the original bases first
 // (saves 2 nx^2 nt + 2 nx nt^2 flops per trial; identical up to rounding).
 struct PredFullFront {
-    double *Bm, *M1, *Kts;       // (nx, R, nt); (2, nz, nx): CSD, LFP; (C, ntstar, nt) = cov_c.compute_Kt(tstar)
+    double *Bm = nullptr, *M1 = nullptr, *Kts = nullptr;     // (nx, R, nt); (2, nz, nx): CSD, LFP; (C, ntstar, nt) = cov_c.compute_Kt(tstar)
+    const double *dz = nullptr, *dts = nullptr;              // the call's sites and times on the device ("pred_z", "pred_tstar")
 };
 // The part of it that reads no trial data (all a posterior variance needs): sites and times to the device, the cross-covariances
 // with M1 = Kc^T Qs per requested output and the cross Grams -- everything that needs only Qs, queued before the join, i.e. it runs
@@ -730,8 +732,8 @@ static void pred_cross_front(gpcsd_ctx *c, const gpcsd_hparams *hp, EigState &e,
     const Geo g = resident_geo(c);
     const int nx = c->nx, nt = c->nt, C = hp->n_temporal;
     hipStream_t s = c->stream;
-    double *dz = c->upload_cached<double>("pred_z", z, (size_t)nz * g.dim);
-    double *dts = c->upload_cached<double>("pred_tstar", tstar, ntstar);
+    const double *dz = f.dz = c->upload_cached<double>("pred_z", z, (size_t)nz * g.dim);
+    const double *dts = f.dts = c->upload_cached<double>("pred_tstar", tstar, ntstar);
     const double *t = (const double *)c->bufs["time_t"].p;
     double *Kc = c->buf<double>("pred_Kcross", (size_t)nx * nz);
     f.Kts = c->buf<double>("pred_Ktstar", (size_t)C * ntstar * nt);
@@ -785,6 +787,15 @@ static PredFullFront predict_full_front(gpcsd_ctx *c, const gpcsd_hparams *hp, E
     pred_data_temporal(c, e, W, f.Bm, c->ntrials);
     return f;
 }
+// S[z][(r,i')] = sum_x' M1[z][x'] Bm[x'][(r,i')] with the M1 of output `which` (1 csd, 2 lfp); RT = columns of Bm: trials x nt
+static void pred_cross_S(gpcsd_ctx *c, const double *M1, int which, int nz, const double *Bm, double *S, long RT) {
+    const int nx = c->nx;
+    GemmDesc g5;
+    g5.M = nz; g5.N = (int)RT; g5.K = nx;
+    g5.A = M1 + (size_t)(which - 1) * nz * nx; g5.lda = nx; g5.B = Bm; g5.ldb = RT; g5.C = S; g5.ldc = RT;
+    g5.prof_name = "gemm_pred_cross";
+    gemm_f64(c, g5, c->stream);
+}
 
 // Posterior mean into ctx-owned device buffers, already in the reference's output layout (z, t, trial):
 //   pred_out_csd / pred_out_lfp            (nz, ntstar, R)
@@ -804,7 +815,7 @@ static int predict_impl(gpcsd_ctx *c, const PredCall &q) {
         return predict_fold(c, q, P, ef);
     }
     EigState e = front_half(c, hp, 0.0);           // no jitter in predict (gpcsd1d.py:258)
-    const int nx = c->nx, nt = c->nt, R = c->ntrials, C = hp->n_temporal;
+    const int nt = c->nt, R = c->ntrials, C = hp->n_temporal;
     const long RT = (long)R * nt;
     hipStream_t s = c->stream;
     // Ktstar_c = cov_c.compute_Kt(tstar): (ntstar, nt); its FIRST axis is contracted with the training
@@ -818,11 +829,7 @@ static int predict_impl(gpcsd_ctx *c, const PredCall &q) {
     for (int which = 1; which <= 2; ++which) {
         if (!(type & which)) continue;
         const PredOut out = pred_out_bufs(c, which, out_elems, C, want_lists);
-        GemmDesc g5;                      // S[z][(r,i')] = sum_x' M1[z][x'] Bm[x'][(r,i')]
-        g5.M = nz; g5.N = (int)RT; g5.K = nx;
-        g5.A = M1 + (size_t)(which - 1) * nz * nx; g5.lda = nx; g5.B = Bm; g5.ldb = RT; g5.C = S; g5.ldc = RT;
-        g5.prof_name = "gemm_pred_cross";
-        gemm_f64(c, g5, s);
+        pred_cross_S(c, M1, which, nz, Bm, S, RT);
         for (int cc = 0; cc < C; ++cc) {
             GemmDesc gp;                  // Pcat[i'][cc*nt + t'] = sum_j Qt[j][i'] Ktstar_cc[j][t']
             gp.M = nt; gp.N = nt; gp.K = ntstar;
@@ -1201,250 +1208,6 @@ extern "C" int gpcsd_predict(gpcsd_ctx *c, const gpcsd_hparams *hp, const double
     replay_if_missed(c, rc, piped, nullptr, nullptr, &q);
     if (rc < 0) return rc;
     pred_download(c, q, sk);
-    c->sync();
-    return rc;
-    GP_API_END(c)
-}
-
-// The temporal operand of the predictions at arbitrary times (gpcsd_predict_at, gpcsd_predict_var, gpcsd_sample_posterior), on the
-// main stream behind the joined temporal side: Pcat[i'][cc * ntstar + j] = sum_i Qt[i][i'] k_cc(t*_j, t_i), the TRAINING axis of the
-// cross Grams Kts (C, ntstar, nt) contracted, the components side by side in "pred_Pc" (nt, C * ntstar).
-static double *pred_at_Pc(gpcsd_ctx *c, const EigState &e, const double *Kts, int C, int ntstar) {
-    const int nt = c->nt;
-    double *Pc = c->buf<double>("pred_Pc", (size_t)C * nt * ntstar);
-    for (int cc = 0; cc < C; ++cc) {
-        GemmDesc gp;
-        gp.M = nt; gp.N = ntstar; gp.K = nt;
-        gp.A = e.Qt; gp.lda = nt; gp.transA = true; gp.B = Kts + (size_t)cc * ntstar * nt; gp.ldb = nt; gp.transB = true;
-        gp.C = Pc + (size_t)cc * ntstar; gp.ldc = (long)C * ntstar;
-        gp.prof_name = "gemm_pred_Pc";
-        gemm_f64(c, gp, c->stream);
-    }
-    return Pc;
-}
-
-// Posterior mean at ARBITRARY prediction times (gpcsd_predict_at; no reference counterpart): as the full-size path of predict_impl
-// up to S = (Kc^T Qs) Bm, then the TRAINING axis of the cross Grams is contracted,
-//   P_c[i'][j] = sum_i Qt[i][i'] k_c(t*_j, t_i),      out_c[z][j][r] = sum_i' S[(z, r)][i'] P_c[i'][j],
-// and the last product writes the output layout itself (gemm_pred_at).  Both sides unfolded: a window of t has no mirror symmetry.
-// Outputs: the buffers of predict_impl, (nz, ntstar, R) / (C, nz, ntstar, R).
-static int predict_at_impl(gpcsd_ctx *c, const PredCall &q) {
-    const gpcsd_hparams *hp = q.hp;
-    const double *z = q.z, *tstar = q.tstar;
-    const int nz = q.nz, ntstar = q.ntstar, type = q.type;
-    const bool want_lists = q.want_lists;
-    GP_REQUIRE(z && tstar && nz > 0 && ntstar > 0, -3, "predict_at: bad arguments");
-    GP_REQUIRE(type >= 1 && type <= 3, -3, "predict_at: type must be CSD(1), LFP(2) or BOTH(3)");
-    GP_REQUIRE(hp != nullptr, -3, "null hparams");
-    GP_REQUIRE(c->d_lfp != nullptr, -4, "lfp not set (call gpcsd_set_lfp)");
-    // (checked before tstar is read: one row of an output, and of the concatenated P_c, is a flat GEMM operand row)
-    GP_REQUIRE((long)c->ntrials * ntstar < GPCSD_MAX_GEMM_LD_KMAJOR && (long)std::max(hp->n_temporal, 1) * ntstar < GPCSD_MAX_GEMM_LD_KMAJOR &&
-                   (long)nz * c->ntrials < (1L << 31),
-               GPCSD_ERR_CAPACITY, "predict_at: ntrials * ntstar = %ld (or n_temporal * ntstar, or nz * ntrials) exceeds the capacity of "
-               "one output row (%ld doubles; GPCSD_MAX_GEMM_LD_KMAJOR)", (long)c->ntrials * ntstar, (long)GPCSD_MAX_GEMM_LD_KMAJOR);
-    EigState e = front_half(c, hp, 0.0);           // no jitter, as predict (gpcsd1d.py:258)
-    const int nx = c->nx, nt = c->nt, R = c->ntrials, C = hp->n_temporal;
-    const long RT = (long)R * nt;
-    hipStream_t s = c->stream;
-    const PredFullFront f = predict_full_front(c, hp, e, z, nz, tstar, ntstar, type);
-    double *const Bm = f.Bm, *const M1 = f.M1, *const Kts = f.Kts;
-    double *S = c->buf<double>("pred_S", (size_t)nz * RT);
-    double *Pc = pred_at_Pc(c, e, Kts, C, ntstar);
-    const size_t out_elems = (size_t)nz * ntstar * R;
-    for (int which = 1; which <= 2; ++which) {
-        if (!(type & which)) continue;
-        const PredOut out = pred_out_bufs(c, which, out_elems, C, want_lists);
-        GemmDesc g5;                      // S[z][(r,i')] = sum_x' M1[z][x'] Bm[x'][(r,i')]
-        g5.M = nz; g5.N = (int)RT; g5.K = nx;
-        g5.A = M1 + (size_t)(which - 1) * nz * nx; g5.lda = nx; g5.B = Bm; g5.ldb = RT; g5.C = S; g5.ldc = RT;
-        g5.prof_name = "gemm_pred_cross";
-        gemm_f64(c, g5, s);
-        PredAtDesc pa;                    // out[cc][z][j][r] = sum_i' Pcat[i'][cc*ntstar + j] S[(z,r)][i'], and the sum over cc
-        pa.S = S; pa.lds = nt; pa.Pc = Pc; pa.ldp = (long)C * ntstar;
-        pa.K = nt; pa.nts = ntstar; pa.C = C; pa.R = R; pa.ncol = (long)nz * R;
-        pa.list = out.list; pa.list_stride = (long)out_elems; pa.sum = out.sum;
-        gemm_pred_at(c, pa, s);
-    }
-    // the resident outputs are this call's now: nothing queued earlier may be evaluated again over them (drain_async, the paired wait)
-    ++c->pred_seq;
-    c->last_pred.have = false;
-    return finish_call(c, e, nullptr, 0);
-}
-
-extern "C" int gpcsd_predict_at_resident(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar,
-                                         int ntstar, int type, int want_lists) {
-    GP_API_BEGIN(c)
-    return predict_at_impl(c, pred_call(hp, z, nz, tstar, ntstar, type, want_lists != 0, false));
-    GP_API_END(c)
-}
-
-extern "C" int gpcsd_predict_at(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar,
-                                int type, double *csd_list, double *csd, double *lfp_list, double *lfp) {
-    GP_API_BEGIN(c)
-    const PredCall q = pred_call(hp, z, nz, tstar, ntstar, type, csd_list != nullptr || lfp_list != nullptr, false);
-    const int rc = predict_at_impl(c, q);
-    if (rc < 0) return rc;
-    PredSink out;
-    out.sum[0] = csd; out.list[0] = csd_list; out.sum[1] = lfp; out.list[1] = lfp_list;
-    pred_download(c, q, out);
-    c->sync();
-    return rc;
-    GP_API_END(c)
-}
-
-// Posterior VARIANCE at the sites and times of gpcsd_predict_at (gpcsd_predict_var; no reference counterpart), of the model whose
-// mean that call returns: D = es (x) et + sig2n exactly as front_half(c, hp, 0.0) builds it.  With M1 = Kcross^T Qs and
-// P_c[i'][j] = sum_i Qt[i][i'] k_c(t*_j, t_i) the explained part of component c at (z, t*_j) is
-//   sum_{x',i'} M1[z][x']^2 P_c[i'][j]^2 / D[x'][i']  =  sum_i' G[z][i'] P_c[i'][j]^2,     G[z][i'] = sum_x' M1[z][x']^2 / D[x'][i'],
-// G formed first and once (it depends on neither t* nor the component), every sum over non-negative terms; the component SUM has
-// (sum_c P_c)^2 in place of P_c^2 -- the components are correlated a posteriori, so it is a plane of its own.  Reads no trial data.
-// Outputs: pred_var_csd / pred_var_lfp (nz, ntstar), pred_var_csd_list / pred_var_lfp_list (C, nz, ntstar).
-static int predict_var_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar, int type) {
-    GP_REQUIRE(z && tstar && nz > 0 && ntstar > 0, -3, "predict_var: bad arguments");
-    GP_REQUIRE(type >= 1 && type <= 3, -3, "predict_var: type must be CSD(1), LFP(2) or BOTH(3)");
-    GP_REQUIRE(hp != nullptr, -3, "null hparams");
-    GP_REQUIRE(c->d_lfp != nullptr, -4, "lfp not set (call gpcsd_set_lfp)");
-    GP_REQUIRE(!uses_host_kt(hp), -3, "predict_var: a user-defined temporal covariance (GPCSD_KIND_HOST) has no prior variance "
-               "k_c(t*, t*) on the device; only the built-in kinds are supported");
-    // (checked before tstar is read: one row of the concatenated P_c is a flat GEMM operand row)
-    GP_REQUIRE((long)std::max(hp->n_temporal, 1) * ntstar < GPCSD_MAX_GEMM_LD_KMAJOR, GPCSD_ERR_CAPACITY,
-               "predict_var: n_temporal * ntstar = %ld exceeds the capacity of one operand row (%ld doubles; GPCSD_MAX_GEMM_LD_KMAJOR)",
-               (long)std::max(hp->n_temporal, 1) * ntstar, (long)GPCSD_MAX_GEMM_LD_KMAJOR);
-    // the scratch of the prediction calls is rewritten below: whatever an earlier queued prediction still owes is collected first
-    if (int rc = drain_async(c)) return rc;
-    EigState e = front_half(c, hp, 0.0);           // no jitter, as predict (gpcsd1d.py:258)
-    const Geo g = resident_geo(c);
-    const int nx = c->nx, nt = c->nt, C = hp->n_temporal;
-    hipStream_t s = c->stream;
-    PredFullFront f{nullptr, nullptr, nullptr};
-    pred_cross_front(c, hp, e, z, nz, tstar, ntstar, type, f);
-    double *Pc = pred_at_Pc(c, e, f.Kts, C, ntstar);
-    double *G = c->buf<double>("pred_var_G", (size_t)nz * nt);
-    double *prior = c->buf<double>("pred_var_prior", (size_t)nz);
-    const double *dz = (const double *)c->bufs["pred_z"].p;
-    const size_t out_elems = (size_t)nz * ntstar;
-    for (int which = 1; which <= 2; ++which) {
-        if (!(type & which)) continue;
-        // prior variance of the spatial factor at the sites: compute_Ks has a unit diagonal (covariances.py:50-56, 177-186); the
-        // potential's is the diagonal of compKphi at the sites themselves (covariances.py:74-96, 204-232)
-        if (which == 1) k_fill(c, prior, nz, 1.0, s);
-        else build_kphi_diag(c, g, hp->R, hp->eps, hp->ell_s, dz, nz, prior, s);
-        VarDesc v1;                       // G[z][i'] = sum_x' M1[z][x']^2 Dinv[x'][i']
-        v1.A = f.M1 + (size_t)(which - 1) * nz * nx; v1.lda = nx; v1.B = e.Dinv; v1.ldb = nt;
-        v1.nrow = nz; v1.ncol = nt; v1.K = nx; v1.sq_a = true; v1.list = G;
-        v1.prof_name = "gemm_var_G";
-        gemm_var(c, v1, s);
-        VarDesc v2;                       // var_c[z][j] = prior[z] k_c(0) - sum_i' G[z][i'] P_c[i'][j]^2, and the component sum's plane
-        v2.A = G; v2.lda = nt; v2.B = Pc; v2.ldb = (long)C * ntstar;
-        v2.nrow = nz; v2.ncol = ntstar; v2.K = nt; v2.C = C;
-        v2.prior = prior;
-        // k_c(t*, t*) = sigma2_c for both built-in kinds (covariances.py:270, 304), rounded as the Gram builders round it
-        for (int cc = 0; cc < C; ++cc) v2.kd[cc] = c->gram_fp32 ? (double)(float)hp->sigma2_t[cc] : hp->sigma2_t[cc];
-        v2.list = c->buf<double>(which == 1 ? "pred_var_csd_list" : "pred_var_lfp_list", out_elems * C);
-        v2.sum = c->buf<double>(which == 1 ? "pred_var_csd" : "pred_var_lfp", out_elems);
-        gemm_var(c, v2, s);
-    }
-    return finish_call(c, e, nullptr, 0);
-}
-
-extern "C" int gpcsd_predict_var_resident(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar,
-                                          int ntstar, int type) {
-    GP_API_BEGIN(c)
-    return predict_var_impl(c, hp, z, nz, tstar, ntstar, type);
-    GP_API_END(c)
-}
-
-extern "C" int gpcsd_predict_var(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar,
-                                 int type, double *csd_var_list, double *csd_var, double *lfp_var_list, double *lfp_var) {
-    GP_API_BEGIN(c)
-    const int rc = predict_var_impl(c, hp, z, nz, tstar, ntstar, type);
-    if (rc < 0) return rc;
-    const size_t out_elems = (size_t)nz * ntstar;
-    double *const sum[2] = {csd_var, lfp_var}, *const list[2] = {csd_var_list, lfp_var_list};
-    for (int w = 0; w < 2; ++w) {
-        if (!(type & (w + 1))) continue;
-        if (sum[w]) c->download(sum[w], c->bufs[w ? "pred_var_lfp" : "pred_var_csd"].p, out_elems * sizeof(double));
-        if (list[w])
-            c->download(list[w], c->bufs[w ? "pred_var_lfp_list" : "pred_var_csd_list"].p, out_elems * hp->n_temporal * sizeof(double));
-    }
-    c->sync();
-    return rc;
-    GP_API_END(c)
-}
-
-// Leave-one-out predictive mean, variance and log score of every training sample (gpcsd_loo; no reference counterpart), of the
-// model whose log-likelihood gpcsd_loglik returns: K = (Qs (x) Qt) diag(D) (Qs (x) Qt)^T exactly as front_half(c, hp, hp->jitter)
-// builds it (the jitter on Ks, a noise list on the eigen-index).  With c = diag(K^-1) and beta_r = K^-1 y_r (Rasmussen & Williams
-// 5.4.2) the score of sample (x, t) of trial r needs no refit:
-//   c[x][t] = sum_{x',i'} Qs[x][x']^2 Qt[t][i']^2 / D[x'][i']          two squared-operand products, every term >= 0
-//   beta_r  = Qs ((Qs^T Y_r Qt) / D) Qt^T                               the prediction front's Bm, V = Qs Bm, then gemm_loo
-// in the merged (unfolded, eigenvector) basis, which is correct for every model the library accepts.  Outputs: loo_var (nx, nt),
-// loo_lpd / loo_sse (nx, R), loo_mean (nx, nt, R) when asked.
-static int loo_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, bool want_mean) {
-    GP_REQUIRE(hp != nullptr, -3, "null hparams");
-    GP_REQUIRE(c->d_lfp != nullptr, -4, "lfp not set (call gpcsd_set_lfp)");
-    const int nx = c->nx, nt = c->nt, R = c->ntrials;
-    const long RT = (long)R * nt, nrow = (long)nx * R;
-    // (checked before anything is read: one row of the projected data is a flat GEMM operand row)
-    GP_REQUIRE(RT < GPCSD_MAX_GEMM_LD_KMAJOR && nrow < (1L << 31), GPCSD_ERR_CAPACITY,
-               "loo: ntrials * nt = %ld (or nx * ntrials = %ld) exceeds the capacity of one operand row (%ld doubles; "
-               "GPCSD_MAX_GEMM_LD_KMAJOR)", RT, nrow, (long)GPCSD_MAX_GEMM_LD_KMAJOR);
-    // the scratch of the prediction calls is rewritten below: whatever an earlier queued prediction still owes is collected first
-    if (int rc = drain_async(c)) return rc;
-    EigState e = front_half(c, hp, hp->jitter);    // the jitter of loglik (gpcsd1d.py:117)
-    hipStream_t s = c->stream;
-    double *W = c->buf<double>("proj_W", (size_t)nx * RT);
-    double *Bm = c->buf<double>("pred_B", (size_t)nx * RT);
-    double *V = c->buf<double>("loo_V", (size_t)nx * RT);
-    double *H = c->buf<double>("loo_H", (size_t)nx * nt);
-    double *QtT = c->buf<double>("loo_QtT", (size_t)nt * nt);
-    double *cdiag = c->buf<double>("loo_c", (size_t)nx * nt);
-    double *var = c->buf<double>("loo_var", (size_t)nx * nt);
-    double *lpd = c->buf<double>("loo_lpd", (size_t)nrow), *sse = c->buf<double>("loo_sse", (size_t)nrow);
-    double *mean = want_mean ? c->buf<double>("loo_mean", (size_t)nx * RT) : nullptr;
-    pred_data_spatial(c, e, W, c->d_lfp, R);
-    join_temporal(c, e, nullptr, false);           // nobody reads sum(log D) here
-    VarDesc v1;                           // H[x][i'] = sum_x' Qs[x][x']^2 Dinv[x'][i']
-    v1.A = e.Qs; v1.lda = nx; v1.B = e.Dinv; v1.ldb = nt;
-    v1.nrow = nx; v1.ncol = nt; v1.K = nx; v1.sq_a = true; v1.list = H;
-    v1.prof_name = "gemm_var_H";
-    gemm_var(c, v1, s);
-    k_swap_last2(c, e.Qt, QtT, 1, nt, nt, s);      // the eigen-index leading: the squared operand's layout
-    VarDesc v2;                           // c[x][t] = sum_i' H[x][i'] Qt[t][i']^2
-    v2.A = H; v2.lda = nt; v2.B = QtT; v2.ldb = nt;
-    v2.nrow = nx; v2.ncol = nt; v2.K = nt; v2.list = cdiag;
-    v2.prof_name = "gemm_var_c";
-    gemm_var(c, v2, s);
-    k_loo_var(c, cdiag, var, (long)nx * nt, s);
-    pred_data_temporal(c, e, W, Bm, R);
-    GemmDesc g3;                          // V[x][(r,i')] = sum_x' Qs[x][x'] Bm[x'][(r,i')]
-    g3.M = nx; g3.N = (int)RT; g3.K = nx;
-    g3.A = e.Qs; g3.lda = nx; g3.B = Bm; g3.ldb = RT; g3.C = V; g3.ldc = RT;
-    g3.prof_name = "gemm_loo_V";
-    gemm_f64(c, g3, s);
-    LooDesc l;                            // beta[(x,r)][t] = sum_i' V[(x,r)][i'] Qt[t][i'], and everything behind it
-    l.V = V; l.ldv = nt; l.Qt = e.Qt; l.ldq = nt; l.c = cdiag; l.y = c->d_lfp;
-    l.K = nt; l.nt = nt; l.R = R; l.nrow = nrow;
-    l.mean = mean; l.lpd = lpd; l.sse = sse;
-    gemm_loo(c, l, s);
-    return finish_call(c, e, nullptr, 0);
-}
-
-extern "C" int gpcsd_loo_resident(gpcsd_ctx *c, const gpcsd_hparams *hp, int want_mean) {
-    GP_API_BEGIN(c)
-    return loo_impl(c, hp, want_mean != 0);
-    GP_API_END(c)
-}
-
-extern "C" int gpcsd_loo(gpcsd_ctx *c, const gpcsd_hparams *hp, double *var, double *mean, double *lpd, double *sse) {
-    GP_API_BEGIN(c)
-    const int rc = loo_impl(c, hp, mean != nullptr);
-    if (rc < 0) return rc;
-    const size_t nxt = (size_t)c->nx * c->nt, nrow = (size_t)c->nx * c->ntrials;
-    if (var) c->download(var, c->bufs["loo_var"].p, nxt * sizeof(double));
-    if (mean) c->download(mean, c->bufs["loo_mean"].p, nxt * c->ntrials * sizeof(double));
-    if (lpd) c->download(lpd, c->bufs["loo_lpd"].p, nrow * sizeof(double));
-    if (sse) c->download(sse, c->bufs["loo_sse"].p, nrow * sizeof(double));
     c->sync();
     return rc;
     GP_API_END(c)

@@ -1,4 +1,4 @@
-// Part of capi.hip (included there: one translation unit, so the file-local helpers of capi.hip and capi_fused.inl are in scope) --
+// Part of capi.hip (included there: one translation unit, so the file-local helpers of capi.hip, capi_fused.inl and capi_posterior.inl are in scope) --
 // missing samples: posterior means and the log-likelihood under a mask of observed samples (gpcsd_predict_masked,
 // gpcsd_loglik_masked) and the assembly of the Schur complement alone (gpcsd_masked_gram).  No reference counterpart.
 //
@@ -269,53 +269,26 @@ static double *masked_core(gpcsd_ctx *c, EigState &e, const MaskPlan &P, const u
 }
 
 // Posterior means with missing samples: gpcsd_predict_at of the model conditioned on the observed samples only.  As predict_at_impl
-// except that the data operand Bm comes from masked_core.  Outputs: the buffers of predict_impl.
+// except that the data operand Bm comes from masked_core (and that it collects an earlier queued prediction first).  Outputs: the buffers of predict_impl.
 static int predict_masked_impl(gpcsd_ctx *c, const PredCall &q, const unsigned char *mask, int mask_trials) {
-    const gpcsd_hparams *hp = q.hp;
-    const int nz = q.nz, ntstar = q.ntstar, type = q.type;
-    GP_REQUIRE(q.z && q.tstar && nz > 0 && ntstar > 0, -3, "predict_masked: bad arguments");
-    GP_REQUIRE(type >= 1 && type <= 3, -3, "predict_masked: type must be CSD(1), LFP(2) or BOTH(3)");
-    masked_check(c, hp, mask, mask_trials, "predict_masked");
-    GP_REQUIRE((long)c->ntrials * ntstar < GPCSD_MAX_GEMM_LD_KMAJOR && (long)std::max(hp->n_temporal, 1) * ntstar < GPCSD_MAX_GEMM_LD_KMAJOR &&
-                   (long)nz * c->ntrials < (1L << 31),
-               GPCSD_ERR_CAPACITY, "predict_masked: ntrials * ntstar = %ld (or n_temporal * ntstar, or nz * ntrials) exceeds the capacity of "
-               "one output row (%ld doubles; GPCSD_MAX_GEMM_LD_KMAJOR)", (long)c->ntrials * ntstar, (long)GPCSD_MAX_GEMM_LD_KMAJOR);
+    posterior_request(c, "predict_masked", q, REQ_SITES);
+    masked_check(c, q.hp, mask, mask_trials, "predict_masked");
+    posterior_request(c, "predict_masked", q, REQ_CAP_OUT_ROW | REQ_CAP_PC_ROW);
     const MaskPlan P = mask_plan(c, mask, mask_trials);              // (capacity: before any data is read)
-    // the scratch of the prediction calls is rewritten below: whatever an earlier queued prediction still owes is collected first
-    if (int rc = drain_async(c)) return rc;
-    EigState e = front_half(c, hp, 0.0);           // no jitter, as predict (gpcsd1d.py:258)
-    const int nx = c->nx, nt = c->nt, R = c->ntrials, C = hp->n_temporal;
-    const long RT = (long)R * nt;
-    hipStream_t s = c->stream;
-    int *st = c->buf<int>("mk_status", 4);
-    GP_HIP(hipMemsetAsync(st, 0, 4 * sizeof(int), s));
-    PredFullFront f{nullptr, nullptr, nullptr};
-    pred_cross_front(c, hp, e, q.z, nz, q.tstar, ntstar, type, f);
-    f.Bm = masked_core(c, e, P, mask, mask_trials, false, st);
-    double *S = c->buf<double>("pred_S", (size_t)nz * RT);
-    double *Pc = pred_at_Pc(c, e, f.Kts, C, ntstar);
-    const size_t out_elems = (size_t)nz * ntstar * R;
+    int *st = nullptr;                                               // a status word for the factorisations
+    PostFront f;
+    const int rc0 = posterior_front(c, q, FRONT_DRAIN, f, [&](EigState &e) {
+        st = c->buf<int>("mk_status", 4);
+        GP_HIP(hipMemsetAsync(st, 0, 4 * sizeof(int), c->stream));
+        return masked_core(c, e, P, mask, mask_trials, false, st);
+    });
+    if (rc0) return rc0;
     {
-        ProfScope ps(c, "masked_tail", 0.0, s);
-        for (int which = 1; which <= 2; ++which) {
-            if (!(type & which)) continue;
-            const PredOut out = pred_out_bufs(c, which, out_elems, C, q.want_lists);
-            GemmDesc g5;                      // S[z][(r,i')] = sum_x' M1[z][x'] Bm[x'][(r,i')]
-            g5.M = nz; g5.N = (int)RT; g5.K = nx;
-            g5.A = f.M1 + (size_t)(which - 1) * nz * nx; g5.lda = nx; g5.B = f.Bm; g5.ldb = RT; g5.C = S; g5.ldc = RT;
-            g5.prof_name = "gemm_pred_cross";
-            gemm_f64(c, g5, s);
-            PredAtDesc pa;                    // out[cc][z][j][r] = sum_i' Pcat[i'][cc*ntstar + j] S[(z,r)][i'], and the sum over cc
-            pa.S = S; pa.lds = nt; pa.Pc = Pc; pa.ldp = (long)C * ntstar;
-            pa.K = nt; pa.nts = ntstar; pa.C = C; pa.R = R; pa.ncol = (long)nz * R;
-            pa.list = out.list; pa.list_stride = (long)out_elems; pa.sum = out.sum;
-            gemm_pred_at(c, pa, s);
-        }
+        ProfScope ps(c, "masked_tail", 0.0, c->stream);
+        pred_mean_outputs(c, f, q);
     }
-    // the resident outputs are this call's now: nothing queued earlier may be evaluated again over them
-    ++c->pred_seq;
-    c->last_pred.have = false;
-    const int rc = finish_call(c, e, nullptr, 0);
+    own_resident_outputs(c);
+    const int rc = finish_call(c, f.e, nullptr, 0);
     const int rc2 = finish_status(c, st);
     return rc != 0 ? rc : rc2;
 }
@@ -334,10 +307,7 @@ extern "C" int gpcsd_predict_masked(gpcsd_ctx *c, const gpcsd_hparams *hp, const
     const PredCall q = pred_call(hp, z, nz, tstar, ntstar, type, csd_list != nullptr || lfp_list != nullptr, false);
     const int rc = predict_masked_impl(c, q, mask, mask_trials);
     if (rc < 0) return rc;
-    PredSink out;
-    out.sum[0] = csd; out.list[0] = csd_list; out.sum[1] = lfp; out.list[1] = lfp_list;
-    pred_download(c, q, out);
-    c->sync();
+    download_sum_list(c, "pred_out_", type, (size_t)nz * ntstar * c->ntrials, hp->n_temporal, csd_list, csd, lfp_list, lfp);
     return rc;
     GP_API_END(c)
 }

@@ -1,4 +1,4 @@
-// Part of capi.hip (included there: one translation unit, so the file-local helpers of capi.hip and capi_fused.inl are in scope) --
+// Part of capi.hip (included there: one translation unit, so the file-local helpers of capi.hip, capi_fused.inl and capi_posterior.inl are in scope) --
 // the device generator's entry point and joint posterior draws of CSD and LFP (gpcsd_sample_posterior).
 
 extern "C" int gpcsd_normals(gpcsd_ctx *c, unsigned long long seed, unsigned stream, unsigned long long first, long count, double *out) {
@@ -45,17 +45,15 @@ static size_t sample_scratch_budget() {
 // The normals of pseudo-trial p are entries [p ns ntt, (p + 1) ns ntt) of stream 0 (Xi) and [p nx nt, (p + 1) nx nt) of stream 1 (E)
 // with p counted from the GLOBAL trial index (gpcsd_ctx::trial_offset): no chunk size, grid or rank changes a normal.
 // Outputs: post_sample_csd / post_sample_lfp (nz, ntstar, R, nsamples).
-static int sample_posterior_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar, int type,
-                                 int nsamples, unsigned long long seed, const double *normals_xi, const double *normals_eps) {
-    GP_REQUIRE(z && tstar && nz > 0 && ntstar > 0, -3, "sample_posterior: bad arguments");
-    GP_REQUIRE(type >= 1 && type <= 3, -3, "sample_posterior: type must be CSD(1), LFP(2) or BOTH(3)");
+static int sample_posterior_impl(gpcsd_ctx *c, const PredCall &q, int nsamples, unsigned long long seed, const double *normals_xi,
+                                 const double *normals_eps) {
+    const gpcsd_hparams *hp = q.hp;
+    const int nz = q.nz, ntstar = q.ntstar, type = q.type;
+    posterior_request(c, "sample_posterior", q, REQ_SITES);
     GP_REQUIRE(nsamples >= 1, -3, "sample_posterior: nsamples=%d must be at least 1", nsamples);
     GP_REQUIRE((normals_xi == nullptr) == (normals_eps == nullptr), -3,
                "sample_posterior: give both normals_xi and normals_eps, or neither (the device generator)");
-    GP_REQUIRE(hp != nullptr, -3, "null hparams");
-    GP_REQUIRE(c->d_lfp != nullptr, -4, "lfp not set (call gpcsd_set_lfp)");
-    GP_REQUIRE(!uses_host_kt(hp), -3, "sample_posterior: a user-defined temporal covariance (GPCSD_KIND_HOST) has no joint Gram over "
-               "[t*; t] on the device; only the built-in kinds are supported");
+    posterior_request(c, "sample_posterior", q, REQ_HP | REQ_LFP | REQ_NO_HOST_KT);
     const int nx = c->nx, nt = c->nt, R = c->ntrials, S = nsamples;
     const int nq = (type & 1) + ((type >> 1) & 1);               // requested quantities
     const long ns_l = (long)nq * nz + nx, ntt_l = (long)ntstar + nt;
@@ -64,7 +62,7 @@ static int sample_posterior_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const do
     GP_REQUIRE(ns_l <= GPCSD_MAX_EIG_N && ntt_l <= GPCSD_MAX_EIG_N, GPCSD_ERR_CAPACITY,
                "sample_posterior: the joint spatial order %ld (sites per requested quantity + electrodes) or temporal order %ld "
                "(ntstar + nt) exceeds the eigensolver's capacity of %d rows (GPCSD_MAX_EIG_N)", ns_l, ntt_l, GPCSD_MAX_EIG_N);
-    const int ns = (int)ns_l, ntt = (int)ntt_l, C = hp->n_temporal;
+    const int ns = (int)ns_l, ntt = (int)ntt_l;
     // doubles of scratch per pseudo-trial: Xi and Xi Ft^T; E, eps, the residual, W and Bm; S; the prior block and the update
     const size_t per = 2 * (size_t)ns * ntt + 5 * (size_t)nx * nt + (size_t)nz * nt + 2 * (size_t)nz * ntstar;
     long chunk = (long)std::max<size_t>(1, sample_scratch_budget() / (per * sizeof(double)));
@@ -73,15 +71,12 @@ static int sample_posterior_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const do
     chunk = std::min(chunk, 65535L);                                      // one batch entry per pseudo-trial
     chunk = std::min(chunk, P);
     GP_REQUIRE(chunk >= 1, GPCSD_ERR_CAPACITY, "sample_posterior: one pseudo-trial alone exceeds the capacity of one operand row");
-    // the scratch of the prediction calls is rewritten below: whatever an earlier queued prediction still owes is collected first
-    if (int rc = drain_async(c)) return rc;
-    EigState e = front_half(c, hp, 0.0);           // no jitter, as predict (gpcsd1d.py:258)
+    PostFront f;                                   // (the trials are read chunk by chunk below, as residuals)
+    if (int rc = posterior_front(c, q, FRONT_DRAIN, f)) return rc;
+    EigState &e = f.e;
     const Geo g = resident_geo(c);
     hipStream_t s = c->stream;
-    PredFullFront f{nullptr, nullptr, nullptr};
-    pred_cross_front(c, hp, e, z, nz, tstar, ntstar, type, f);
-    double *Pc = pred_at_Pc(c, e, f.Kts, C, ntstar);
-    const double *dz = (const double *)c->bufs["pred_z"].p, *dts = (const double *)c->bufs["pred_tstar"].p;
+    const double *dz = f.dz, *dts = f.dts;
     const double *t = (const double *)c->bufs["time_t"].p;
     int *st = c->buf<int>("sp_status", 4);
     GP_HIP(hipMemsetAsync(st, 0, 4 * sizeof(int), s));
@@ -142,7 +137,7 @@ static int sample_posterior_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const do
     double *Xi = c->buf<double>("sp_Xi", cn * ns * ntt), *T1 = c->buf<double>("sp_T1", cn * ns * ntt);
     double *E = c->buf<double>("sp_E", cn * nx * nt), *eps = c->buf<double>("sp_eps", cn * nx * nt);
     double *res = c->buf<double>("sp_res", cn * nx * nt);
-    double *W = c->buf<double>("proj_W", cn * nx * nt), *Bm = c->buf<double>("pred_B", cn * nx * nt);
+    double *W = c->buf<double>("proj_W", cn * nx * nt), *Bm = f.Bm = c->buf<double>("pred_B", cn * nx * nt);
     double *Sm = c->buf<double>("pred_S", cn * nz * nt);
     double *fp = c->buf<double>("sp_prior", cn * nz * ntstar), *upd = c->buf<double>("sp_upd", cn * nz * ntstar);
     double *out[2] = {nullptr, nullptr};
@@ -189,16 +184,7 @@ static int sample_posterior_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, const do
             g4.batch = np; g4.sB = (long)ns * ntt; g4.sC = ntstar;
             g4.prof_name = "gemm_sample_spatial";
             gemm_f64(c, g4, s);
-            GemmDesc g5;                  // S[z][(q,i')] = sum_x' M1[z][x'] Bm[x'][(q,i')]
-            g5.M = nz; g5.N = (int)RT; g5.K = nx;
-            g5.A = f.M1 + (size_t)(which - 1) * nz * nx; g5.lda = nx; g5.B = Bm; g5.ldb = RT; g5.C = Sm; g5.ldc = RT;
-            g5.prof_name = "gemm_pred_cross";
-            gemm_f64(c, g5, s);
-            PredAtDesc pa;                // upd[z][j][q] = sum_cc sum_i' Pcat[i'][cc*ntstar + j] S[(z,q)][i']
-            pa.S = Sm; pa.lds = nt; pa.Pc = Pc; pa.ldp = (long)C * ntstar;
-            pa.K = nt; pa.nts = ntstar; pa.C = C; pa.R = np; pa.ncol = (long)nz * np;
-            pa.list = nullptr; pa.list_stride = 0; pa.sum = upd;
-            gemm_pred_at(c, pa, s);
+            pred_mean_tail(c, f, q, which, np, Sm, upd, nullptr, 0);     // upd[z][j][q] = P (the residuals), the components summed
             k_sample_combine(c, upd, fp, out[which - 1], nz, ntstar, np, P, p0, s);     // the one add pass: + f_prior, into (z, t*, p)
         }
     }
@@ -211,7 +197,7 @@ extern "C" int gpcsd_sample_posterior_resident(gpcsd_ctx *c, const gpcsd_hparams
                                                int ntstar, int type, int nsamples, unsigned long long seed, const double *normals_xi,
                                                const double *normals_eps) {
     GP_API_BEGIN(c)
-    return sample_posterior_impl(c, hp, z, nz, tstar, ntstar, type, nsamples, seed, normals_xi, normals_eps);
+    return sample_posterior_impl(c, pred_call(hp, z, nz, tstar, ntstar, type, false, false), nsamples, seed, normals_xi, normals_eps);
     GP_API_END(c)
 }
 
@@ -219,12 +205,10 @@ extern "C" int gpcsd_sample_posterior(gpcsd_ctx *c, const gpcsd_hparams *hp, con
                                       int type, int nsamples, unsigned long long seed, const double *normals_xi,
                                       const double *normals_eps, double *csd, double *lfp) {
     GP_API_BEGIN(c)
-    const int rc = sample_posterior_impl(c, hp, z, nz, tstar, ntstar, type, nsamples, seed, normals_xi, normals_eps);
+    const int rc = sample_posterior_impl(c, pred_call(hp, z, nz, tstar, ntstar, type, false, false), nsamples, seed, normals_xi, normals_eps);
     if (rc < 0) return rc;
-    const size_t bytes = (size_t)nz * ntstar * c->ntrials * nsamples * sizeof(double);
-    if (csd && (type & 1)) c->download(csd, c->bufs["post_sample_csd"].p, bytes);
-    if (lfp && (type & 2)) c->download(lfp, c->bufs["post_sample_lfp"].p, bytes);
-    c->sync();
+    const size_t count = (size_t)nz * ntstar * c->ntrials * nsamples;
+    download_outputs(c, {{(type & 1) ? csd : nullptr, "post_sample_csd", count}, {(type & 2) ? lfp : nullptr, "post_sample_lfp", count}});
     return rc;
     GP_API_END(c)
 }

@@ -691,16 +691,31 @@ class GPCSDModel:
         return None
 
     # ------------------------------------------------------------------ prediction
+    _TYPE_CODES = {"csd": _hip.PRED_CSD, "lfp": _hip.PRED_LFP, "both": _hip.PRED_BOTH}
     _PRED_BUFFERS = (("csd", _hip.PRED_CSD, "pred_out_csd"), ("lfp", _hip.PRED_LFP, "pred_out_lfp"))
+    _VAR_BUFFERS = (("csd", _hip.PRED_CSD, "pred_var_csd"), ("lfp", _hip.PRED_LFP, "pred_var_lfp"))
 
-    def _device_predictions(self, ctx, code, nz, nt, R_local):
-        """Zero-copy views (`_hip.DeviceArray`) of the posterior means a resident prediction left in HBM."""
+    def _posterior_request(self, z, tstar, type, any_times=False):
+        """What every posterior call at sites z and times tstar starts from: (z as float64, its (nz, dim) form, tstar as an array,
+        the code of `type`).  ValueError on an unknown type and -- unless any_times (predict) -- on an empty tstar.  Opens no context."""
+        if type not in self._TYPE_CODES:
+            raise ValueError("type must be 'csd', 'lfp' or 'both'")
+        z = np.asarray(z, dtype=np.float64)
+        z2 = z.reshape(-1, 1) if self.dim == 1 else z
+        tstar = np.asarray(tstar)
+        if tstar.size < 1 and not any_times:
+            raise ValueError("tstar must hold at least one time")
+        return z, z2, tstar, self._TYPE_CODES[type]
+
+    def _device_predictions(self, ctx, code, shape, buffers=_PRED_BUFFERS):
+        """Zero-copy views (`_hip.DeviceArray`) of what a resident call left in HBM under `buffers`: per requested quantity the
+        array of `shape` and its "_list" form with a leading axis of the temporal components."""
         C = len(self.temporal_cov_list)
         res = {}
-        for name, bit, buf in self._PRED_BUFFERS:
+        for name, bit, buf in buffers:
             if code & bit:
-                res[name] = ctx.device_array(buf, (nz, nt, R_local))
-                res[name + "_list"] = ctx.device_array(buf + "_list", (C, nz, nt, R_local))
+                res[name] = ctx.device_array(buf, tuple(shape))
+                res[name + "_list"] = ctx.device_array(buf + "_list", (C,) + tuple(shape))
         return res
 
     def _store_predictions(self, res, z, t):
@@ -720,25 +735,24 @@ class GPCSDModel:
         (`__cuda_array_interface__`, float64, (nz, nt, ntrials); the `*_list` attributes (C, nz, nt, ntrials)) instead of NumPy
         arrays -- `torch.as_tensor(m.csd_pred, device="cuda")` -- valid until the model's next prediction.  Returning host arrays
         is bound by the PCIe link (231 MB per call at 384 x 500 x 50), the resident form by the GPU."""
-        if type not in ("csd", "lfp", "both"):
-            raise ValueError("type must be 'csd', 'lfp' or 'both'")
+        self._predict_mean(z, t, type, resident, at=False)
+
+    def _predict_mean(self, z, t, type, resident, at):
+        """predict (at=False: t is not checked, the reference's contraction) and predict_at (at=True)."""
+        z, z2, t, code = self._posterior_request(z, t, type, any_times=not at)
         ctx = self._sync_device()
-        z = np.asarray(z, dtype=np.float64)
-        z2 = z.reshape(-1, 1) if self.dim == 1 else z
-        t = np.asarray(t)
         hp, _keep = self._hparams(0.0, tstar=t)            # no jitter in predict
-        code = {"csd": _hip.PRED_CSD, "lfp": _hip.PRED_LFP, "both": _hip.PRED_BOTH}[type]
-        R_local = self._local_lfp().shape[2]
+        shape = (z2.shape[0], t.size if at else t.shape[0], self._local_lfp().shape[2])
         sh = getattr(self, "_sharding", None)
         gather = sh is not None and getattr(sh, "gather_predictions", False)
         if resident or (gather and sh.on_device()):
-            ctx.predict_resident(hp, z2, t, code, want_lists=True)
-            res = self._device_predictions(ctx, code, z2.shape[0], t.shape[0], R_local)
+            ctx.predict_resident(hp, z2, t, code, want_lists=True, at=at)
+            res = self._device_predictions(ctx, code, shape)
             if gather:
                 # trial blocks gathered ON THE DEVICE (RCCL all-gather over xGMI), one copy out on the gathering rank(s) only
                 res = {k: sh.gather_trials_device(v, dst=getattr(sh, "gather_dst", None)) for k, v in res.items()}
         else:
-            res = ctx.predict(hp, z2, t, code, (z2.shape[0], t.shape[0], R_local))
+            res = ctx.predict(hp, z2, t, code, shape, at=at)
             if gather:
                 res = {k: sh.gather_trials(v) for k, v in res.items()}
         self._store_predictions(res, z, t)
@@ -750,29 +764,7 @@ class GPCSDModel:
         Unlike `predict(z, t)`, which for t other than the training grid reproduces the reference's contraction of the test axis of
         compute_Kt(t) (gpcsd1d.py:277-279), this contracts the training axis and so is the GP prediction at tstar; the two agree
         when t is the training grid.  No reference counterpart."""
-        if type not in ("csd", "lfp", "both"):
-            raise ValueError("type must be 'csd', 'lfp' or 'both'")
-        ctx = self._sync_device()
-        z = np.asarray(z, dtype=np.float64)
-        z2 = z.reshape(-1, 1) if self.dim == 1 else z
-        tstar = np.asarray(tstar)
-        if tstar.size < 1:
-            raise ValueError("tstar must hold at least one time")
-        hp, _keep = self._hparams(0.0, tstar=tstar)        # no jitter, as predict
-        code = {"csd": _hip.PRED_CSD, "lfp": _hip.PRED_LFP, "both": _hip.PRED_BOTH}[type]
-        R_local = self._local_lfp().shape[2]
-        sh = getattr(self, "_sharding", None)
-        gather = sh is not None and getattr(sh, "gather_predictions", False)
-        if resident or (gather and sh.on_device()):
-            ctx.predict_resident(hp, z2, tstar, code, want_lists=True, at=True)
-            res = self._device_predictions(ctx, code, z2.shape[0], tstar.size, R_local)
-            if gather:
-                res = {k: sh.gather_trials_device(v, dst=getattr(sh, "gather_dst", None)) for k, v in res.items()}
-        else:
-            res = ctx.predict(hp, z2, tstar, code, (z2.shape[0], tstar.size, R_local), at=True)
-            if gather:
-                res = {k: sh.gather_trials(v) for k, v in res.items()}
-        self._store_predictions(res, z, tstar)
+        self._predict_mean(z, tstar, type, resident, at=True)
 
     def _masked_args(self, mask, who):
         if getattr(self, "_sharding", None) is not None:
@@ -798,23 +790,16 @@ class GPCSDModel:
         without an observed sample predicts 0.  More than 8192 missing samples in one trial (GPCSD_MAX_MISSING) raise
         GPCSDCapacityError.  ValueError on a mask of another shape; NotImplementedError on trial-sharded models and on user-defined
         temporal covariances.  No reference counterpart."""
-        if type not in ("csd", "lfp", "both"):
-            raise ValueError("type must be 'csd', 'lfp' or 'both'")
+        z, z2, tstar, code = self._posterior_request(z, tstar, type)
         mask = self._masked_args(mask, "predict_masked")
         ctx = self._sync_device()
-        z = np.asarray(z, dtype=np.float64)
-        z2 = z.reshape(-1, 1) if self.dim == 1 else z
-        tstar = np.asarray(tstar)
-        if tstar.size < 1:
-            raise ValueError("tstar must hold at least one time")
         hp, _keep = self._hparams(0.0)                     # no jitter, as predict
-        code = {"csd": _hip.PRED_CSD, "lfp": _hip.PRED_LFP, "both": _hip.PRED_BOTH}[type]
-        R = np.shape(self.lfp)[2]
+        shape = (z2.shape[0], tstar.size, np.shape(self.lfp)[2])
         if resident:
             ctx.predict_masked_resident(hp, mask, z2, tstar, code, want_lists=True)
-            res = self._device_predictions(ctx, code, z2.shape[0], tstar.size, R)
+            res = self._device_predictions(ctx, code, shape)
         else:
-            res = ctx.predict_masked(hp, mask, z2, tstar, code, (z2.shape[0], tstar.size, R))
+            res = ctx.predict_masked(hp, mask, z2, tstar, code, shape)
         self._store_predictions(res, z, tstar)
         return res
 
@@ -832,8 +817,6 @@ class GPCSDModel:
         self.n_obs = n_obs
         return np.float64(-0.5 * ld - 0.5 * qd)
 
-    _VAR_BUFFERS = (("csd", _hip.PRED_CSD, "pred_var_csd"), ("lfp", _hip.PRED_LFP, "pred_var_lfp"))
-
     def predict_var(self, z, tstar, type="csd", resident=False):
         """Posterior VARIANCE of CSD and/or LFP at sites z and arbitrary times tstar: the diagonal of the posterior covariance of the
         model whose mean `predict_at(z, tstar)` returns (no jitter; a per-electrode noise list on the eigen-index as in loglik).  It
@@ -847,27 +830,16 @@ class GPCSDModel:
         caller's signal that the band is below the resolution of float64 there, not something to hide.  Under trial sharding every
         rank computes the same arrays locally (no communication; `gather_predictions` does not apply).  User-defined temporal
         covariances are not supported (no prior variance on the device): NotImplementedError.  No reference counterpart."""
-        if type not in ("csd", "lfp", "both"):
-            raise ValueError("type must be 'csd', 'lfp' or 'both'")
-        z = np.asarray(z, dtype=np.float64)
-        z2 = z.reshape(-1, 1) if self.dim == 1 else z
-        tstar = np.asarray(tstar)
-        if tstar.size < 1:
-            raise ValueError("tstar must hold at least one time")
+        z, z2, tstar, code = self._posterior_request(z, tstar, type)
         if self._uses_host_kt():
             raise NotImplementedError("predict_var: a user-defined temporal covariance has no prior variance k(t*, t*) on the device; "
                                       "only GPCSDTemporalCovSE / GPCSDTemporalCovMatern components are supported")
         ctx = self._sync_device()
         hp, _keep = self._hparams(0.0)                     # no jitter, as predict
-        code = {"csd": _hip.PRED_CSD, "lfp": _hip.PRED_LFP, "both": _hip.PRED_BOTH}[type]
-        nz, nts, C = z2.shape[0], tstar.size, len(self.temporal_cov_list)
+        C = len(self.temporal_cov_list)
         if resident:
             ctx.predict_var_resident(hp, z2, tstar, code)
-            res = {}
-            for name, bit, buf in self._VAR_BUFFERS:
-                if code & bit:
-                    res[name] = ctx.device_array(buf, (nz, nts))
-                    res[name + "_list"] = ctx.device_array(buf + "_list", (C, nz, nts))
+            res = self._device_predictions(ctx, code, (z2.shape[0], tstar.size), self._VAR_BUFFERS)
         else:
             res = ctx.predict_var(hp, z2, tstar, code)
         for name in ("csd", "lfp"):
@@ -906,13 +878,7 @@ class GPCSDModel:
         as in `predict_at`; `gather_predictions` does not apply.  User-defined temporal covariances are not supported (no k(t*, t*)
         on the device): NotImplementedError.  GPCSDCapacityError when the scratch (n_components * J * nx * nt doubles and about as
         much again) exceeds GPCSD_FUN_SCRATCH_MB megabytes (default 2048).  No reference counterpart."""
-        if type not in ("csd", "lfp", "both"):
-            raise ValueError("type must be 'csd', 'lfp' or 'both'")
-        z = np.asarray(z, dtype=np.float64)
-        z2 = z.reshape(-1, 1) if self.dim == 1 else z
-        tstar = np.asarray(tstar)
-        if tstar.size < 1:
-            raise ValueError("tstar must hold at least one time")
+        z, z2, tstar, code = self._posterior_request(z, tstar, type)
         W = np.ascontiguousarray(W, dtype=np.float64)
         nz, nts = z2.shape[0], tstar.size
         if W.ndim != 3 or W.shape[0] < 1 or W.shape[1:] != (nz, nts):
@@ -924,7 +890,6 @@ class GPCSDModel:
                                       "device; only GPCSDTemporalCovSE / GPCSDTemporalCovMatern components are supported")
         ctx = self._sync_device()
         hp, _keep = self._hparams(0.0)                     # no jitter, as predict
-        code = {"csd": _hip.PRED_CSD, "lfp": _hip.PRED_LFP, "both": _hip.PRED_BOTH}[type]
         J, C, R_local = W.shape[0], len(self.temporal_cov_list), self._local_lfp().shape[2]
         if resident:
             ctx.predict_functionals_resident(hp, z2, tstar, W, code)
@@ -1317,7 +1282,7 @@ class GPCSDModel:
         z = np.asarray(z, dtype=np.float64)
         z2 = np.ascontiguousarray(z.reshape(-1, 1) if self.dim == 1 else z)
         t = np.asarray(t)
-        code = {"csd": _hip.PRED_CSD, "lfp": _hip.PRED_LFP, "both": _hip.PRED_BOTH}[type]
+        code = self._TYPE_CODES[type]
         sets = []
         for p in param_sets:                               # every set's two hyper-parameter structs, before anything is queued
             self.restore_model_params(p)
@@ -1340,7 +1305,7 @@ class GPCSDModel:
                 out[k] = -0.5 * ntrials * sumlog - 0.5 * quad
         finally:
             ctx.pair_share_s(was)
-        res = self._device_predictions(ctx, code, z2.shape[0], t.shape[0], R_local)
+        res = self._device_predictions(ctx, code, (z2.shape[0], t.shape[0], R_local))
         gather = sh is not None and getattr(sh, "gather_predictions", False)
         if gather and sh.on_device():
             res = {k: sh.gather_trials_device(v, dst=getattr(sh, "gather_dst", None)) for k, v in res.items()}
@@ -1355,13 +1320,7 @@ class GPCSDModel:
 
     def _sample_posterior_args(self, z, tstar, type, nsamples):
         """Validation and shapes shared by sample_posterior and _sample_posterior_from_normals; opens no context."""
-        if type not in ("csd", "lfp", "both"):
-            raise ValueError("type must be 'csd', 'lfp' or 'both'")
-        z = np.asarray(z, dtype=np.float64)
-        z2 = z.reshape(-1, 1) if self.dim == 1 else z
-        tstar = np.asarray(tstar)
-        if tstar.size < 1:
-            raise ValueError("tstar must hold at least one time")
+        _z, z2, tstar, code = self._posterior_request(z, tstar, type)
         if int(nsamples) < 1:
             raise ValueError("nsamples must be at least 1")
         if self._uses_host_kt():
@@ -1370,7 +1329,6 @@ class GPCSDModel:
         sh = getattr(self, "_sharding", None)
         if sh is not None and getattr(sh, "gather_predictions", False):
             raise NotImplementedError("sample_posterior: gather_predictions does not apply to draws; each rank returns its block of trials")
-        code = {"csd": _hip.PRED_CSD, "lfp": _hip.PRED_LFP, "both": _hip.PRED_BOTH}[type]
         return z2, tstar, code, sh
 
     def _sample_posterior_call(self, z2, tstar, code, sh, nsamples, seed, xi, eps, resident):
