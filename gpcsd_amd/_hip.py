@@ -20,6 +20,8 @@ ERR_CAPACITY = -7
 MAX_EIG_N = 4096                 # GPCSD_MAX_EIG_N: rows of one eigenproblem (after symmetry folding)
 MAX_GEMM_LD_KMAJOR = 1 << 23     # GPCSD_MAX_GEMM_LD_KMAJOR: ntrials * nt of one resident block of trials
 MAX_MISSING = 8192               # GPCSD_MAX_MISSING: missing samples of one trial in the masked calls
+MAX_REGIONS = 4096               # GPCSD_MAX_REGIONS: labelled regions of region_features / sample_features
+NFEAT = 10                       # GPCSD_NFEAT: values per region and column of those calls
 PRED_CSD, PRED_LFP, PRED_BOTH = 1, 2, 3
 
 _c_double_p = ctypes.POINTER(ctypes.c_double)
@@ -112,6 +114,7 @@ _D = ctypes.c_double
 _I = ctypes.c_int
 _L = ctypes.c_long
 _DP = _c_double_p
+_IP = ctypes.POINTER(ctypes.c_int)
 SIGNATURES = {
     "gpcsd_ctx_create": (_I, [_I, ctypes.POINTER(_P)]),
     "gpcsd_ctx_destroy": (_I, [_P]),
@@ -203,6 +206,12 @@ SIGNATURES = {
     "gpcsd_masked_gram": (_I, [_P, _DP, _I, _DP, _I, _DP, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _I, _DP]),
     "gpcsd_sample_posterior": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _I, ctypes.c_ulonglong, _DP, _DP, _DP, _DP]),
     "gpcsd_sample_posterior_resident": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _I, ctypes.c_ulonglong, _DP, _DP]),
+    "gpcsd_region_features": (_I, [_P, _DP, _I, _I, _L, _IP, _I, _DP, _DP, _I, _DP, _DP, _I, _I, _DP]),
+    "gpcsd_region_features_resident": (_I, [_P, ctypes.c_char_p, _L, _I, _I, _L, _IP, _I, _DP, _DP, _I, _DP, _DP, _I, _I]),
+    "gpcsd_sample_features": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _I, ctypes.c_ulonglong, _DP, _DP, _IP, _I, _I, _D,
+                                   _I, _DP, _DP, _DP, _DP]),
+    "gpcsd_sample_features_resident": (_I, [_P, ctypes.POINTER(HParams), _DP, _I, _DP, _I, _I, _I, ctypes.c_ulonglong, _DP, _DP, _IP, _I,
+                                            _I, _D, _I]),
     "gpcsd_set_gram_precision": (_I, [_P, _I]),
     "gpcsd_fold_gemm": (_I, [_P, _I, ctypes.POINTER(_L)]),
     "gpcsd_ll_tridiag": (_I, [_P, _I, ctypes.POINTER(_L)]),
@@ -1378,6 +1387,80 @@ class Context:
                 for name, bit in (("csd", PRED_CSD), ("lfp", PRED_LFP))}
         self._check(self._lib.gpcsd_sample_posterior(*args, _ptr(bufs["csd"]), _ptr(bufs["lfp"])))
         return {k: v for k, v in bufs.items() if v is not None}
+
+    # ---- region features of a field and of posterior draws (features.hip) ----
+    @staticmethod
+    def _feature_operands(nz, nts, M, labels, tau, zeta, mean, isd, S):
+        """The host operands of the region-feature calls as the C ABI reads them; ValueError on a shape that does not fit."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if labels.shape != (nz, nts):
+            raise ValueError("labels must have shape (%d, %d), not %s" % (nz, nts, labels.shape))
+        tau = _arr(tau).reshape(-1)
+        zeta = _arr(zeta)
+        zeta = zeta.reshape(-1, 1) if zeta.ndim == 1 else zeta
+        if tau.size != nts or zeta.ndim != 2 or zeta.shape[0] != nz or zeta.shape[1] not in (1, 2):
+            raise ValueError("the coordinates must be (%d,) times and (%d, 1 or 2) sites" % (nts, nz))
+        if (mean is None) != (isd is None):
+            raise ValueError("give both mean and isd, or neither")
+        R = 0
+        if mean is not None:
+            mean, isd = _arr(mean), _arr(isd)
+            if mean.ndim != 3 or mean.shape[:2] != (nz, nts) or mean.shape[2] * int(S) != M or isd.shape != (nz, nts):
+                raise ValueError("mean must be (%d, %d, R) with R * %d = %d columns and isd (%d, %d)" % (nz, nts, S, M, nz, nts))
+            R = mean.shape[2]
+        return labels, tau, zeta, mean, isd, R
+
+    def region_features(self, x, labels, J, tau, zeta, mean=None, isd=None, S=1):
+        """Region features of the host field x (nz, nts, M) (gpcsd_region_features): (J, NFEAT, M), slots as the header lists them."""
+        x = _arr(x)
+        if x.ndim != 3:
+            raise ValueError("region_features: x must be (nz, nts, M)")
+        nz, nts, M = x.shape
+        labels, tau, zeta, mean, isd, R = self._feature_operands(nz, nts, M, labels, tau, zeta, mean, isd, S)
+        out = pinned_pool.empty((int(J), NFEAT, M))
+        self._check(self._lib.gpcsd_region_features(self._h, _ptr(x), nz, nts, M, labels.ctypes.data_as(_IP), int(J), _ptr(tau), _ptr(zeta),
+                                                    zeta.shape[1], _ptr(mean), _ptr(isd), R, int(S), _ptr(out)))
+        return out
+
+    def region_features_resident(self, src_name, src_offset, shape, labels, J, tau, zeta, mean=None, isd=None, S=1):
+        """The same on the named device buffer `src_name` from `src_offset` doubles on, read as shape = (nz, nts, M)
+        (gpcsd_region_features_resident); the features stay in "feat_out", returned as a zero-copy view (J, NFEAT, M)."""
+        nz, nts, M = (int(v) for v in shape)
+        labels, tau, zeta, mean, isd, R = self._feature_operands(nz, nts, M, labels, tau, zeta, mean, isd, S)
+        self._check(self._lib.gpcsd_region_features_resident(self._h, src_name.encode(), int(src_offset), nz, nts, M,
+                                                             labels.ctypes.data_as(_IP), int(J), _ptr(tau), _ptr(zeta), zeta.shape[1],
+                                                             _ptr(mean), _ptr(isd), R, int(S)))
+        return self.device_array("feat_out", (int(J), NFEAT, M))
+
+    def sample_features(self, hp, z, tstar, type_code, nsamples, seed, R, labels, J, band=False, floor=1e-10, keep_draws=False,
+                        xi=None, eps=None, resident=False):
+        """Region features of posterior draws, reduced inside the sampler (gpcsd_sample_features): dict with "feat_csd" / "feat_lfp"
+        (J, NFEAT, R * nsamples) and, with keep_draws, "csd" / "lfp" (nz, ntstar, R, nsamples) for the requested type -- host arrays,
+        or with resident=True zero-copy views of "feat_csd" / "feat_lfp" and "post_sample_csd" / "post_sample_lfp"."""
+        z, tstar = _sites_times(z, tstar)
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if labels.shape != (z.shape[0], tstar.size):
+            raise ValueError("labels must have shape (%d, %d), not %s" % (z.shape[0], tstar.size, labels.shape))
+        xi = None if xi is None else _arr(xi)
+        eps = None if eps is None else _arr(eps)
+        args = (self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size, int(type_code), int(nsamples), int(seed),
+                _ptr(xi), _ptr(eps), labels.ctypes.data_as(_IP), int(J), int(bool(band)), float(floor), int(bool(keep_draws)))
+        quantities = [(name, buf) for name, bit, buf in (("csd", PRED_CSD, "post_sample_csd"), ("lfp", PRED_LFP, "post_sample_lfp"))
+                      if type_code & bit]
+        fshape = (int(J), NFEAT, int(R) * int(nsamples))
+        dshape = (z.shape[0], tstar.size, int(R), int(nsamples))
+        if resident:
+            self._check(self._lib.gpcsd_sample_features_resident(*args))
+            res = {"feat_" + name: self.device_array("feat_" + name, fshape) for name, _ in quantities}
+            if keep_draws:
+                res.update({name: self.device_array(buf, dshape) for name, buf in quantities})
+            return res
+        res = {"feat_" + name: pinned_pool.empty(fshape) for name, _ in quantities}
+        if keep_draws:
+            res.update({name: pinned_pool.empty(dshape) for name, _ in quantities})
+        self._check(self._lib.gpcsd_sample_features(*args, _ptr(res.get("feat_csd")), _ptr(res.get("feat_lfp")), _ptr(res.get("csd")),
+                                                    _ptr(res.get("lfp"))))
+        return res
 
     # ---- measurement ----
     def synchronize(self):

@@ -1414,6 +1414,7 @@ extern "C" int gpcsd_set_time(gpcsd_ctx *c, const double *t, int nt) {
 #include "capi_fused.inl"
 #include "capi_posterior.inl"
 #include "capi_sample.inl"
+#include "capi_features.inl"
 #include "capi_functionals.inl"
 #include "capi_masked.inl"
 #include "capi_phase.inl"

@@ -186,9 +186,10 @@ extern "C" int gpcsd_predict_at(gpcsd_ctx *c, const gpcsd_hparams *hp, const dou
 //   sum_{x',i'} M1[z][x']^2 P_c[i'][j]^2 / D[x'][i']  =  sum_i' G[z][i'] P_c[i'][j]^2,     G[z][i'] = sum_x' M1[z][x']^2 / D[x'][i'],
 // G formed first and once (it depends on neither t* nor the component), every sum over non-negative terms; the component SUM has
 // (sum_c P_c)^2 in place of P_c^2 -- the components are correlated a posteriori, so it is a plane of its own.  Reads no trial data.
-// Outputs: pred_var_csd / pred_var_lfp (nz, ntstar), pred_var_csd_list / pred_var_lfp_list (C, nz, ntstar).
+// Outputs: pred_var_csd / pred_var_lfp (nz, ntstar), pred_var_csd_list / pred_var_lfp_list (C, nz, ntstar) -- or under another
+// prefix, for a call that needs the variance and must leave the caller's alone (gpcsd_sample_features).
 // ------------------------------------------------------------------------------------------------------------------
-static int predict_var_impl(gpcsd_ctx *c, const PredCall &q) {
+static int predict_var_impl(gpcsd_ctx *c, const PredCall &q, const std::string &prefix = "pred_var_") {
     posterior_request(c, "predict_var", q, REQ_SITES | REQ_HP | REQ_LFP | REQ_NO_HOST_KT | REQ_CAP_PC_ROW);
     PostFront f;
     if (int rc = posterior_front(c, q, FRONT_DRAIN, f)) return rc;
@@ -216,8 +217,9 @@ static int predict_var_impl(gpcsd_ctx *c, const PredCall &q) {
         v2.prior = prior;
         // k_c(t*, t*) = sigma2_c for both built-in kinds (covariances.py:270, 304), rounded as the Gram builders round it
         for (int cc = 0; cc < C; ++cc) v2.kd[cc] = c->gram_fp32 ? (double)(float)hp->sigma2_t[cc] : hp->sigma2_t[cc];
-        v2.list = c->buf<double>(which == 1 ? "pred_var_csd_list" : "pred_var_lfp_list", out_elems * C);
-        v2.sum = c->buf<double>(which == 1 ? "pred_var_csd" : "pred_var_lfp", out_elems);
+        const std::string name = prefix + (which == 1 ? "csd" : "lfp");
+        v2.list = c->buf<double>(name + "_list", out_elems * C);
+        v2.sum = c->buf<double>(name, out_elems);
         gemm_var(c, v2, s);
     }
     return finish_call(c, f.e, nullptr, 0);

@@ -45,8 +45,17 @@ static size_t sample_scratch_budget() {
 // The normals of pseudo-trial p are entries [p ns ntt, (p + 1) ns ntt) of stream 0 (Xi) and [p nx nt, (p + 1) nx nt) of stream 1 (E)
 // with p counted from the GLOBAL trial index (gpcsd_ctx::trial_offset): no chunk size, grid or rank changes a normal.
 // Outputs: post_sample_csd / post_sample_lfp (nz, ntstar, R, nsamples).
+// sink (gpcsd_sample_features): a consumer of every chunk's draws where the combine pass left them.  Its scratch counts in the chunk
+// length whether or not the draws are kept, so that both settings form the same draws; without a sink nothing here changes.
+struct SampleSink {
+    bool keep_draws = true;                // false: the combine writes a chunk-sized scratch, post_sample_* is not allocated
+    size_t per_extra = 0;                  // doubles of the consumer's scratch per pseudo-trial, the chunk's draws included
+    std::function<int()> prelude;          // runs after every check, before anything of the sampler is queued
+    // the draws of quantity `which` (1 csd, 2 lfp) of pseudo-trials [p0, p0 + np): F[point][q], rows of ld doubles
+    std::function<void(int which, const double *F, long ld, long p0, int np)> consume;
+};
 static int sample_posterior_impl(gpcsd_ctx *c, const PredCall &q, int nsamples, unsigned long long seed, const double *normals_xi,
-                                 const double *normals_eps) {
+                                 const double *normals_eps, const SampleSink *sink = nullptr) {
     const gpcsd_hparams *hp = q.hp;
     const int nz = q.nz, ntstar = q.ntstar, type = q.type;
     posterior_request(c, "sample_posterior", q, REQ_SITES);
@@ -64,13 +73,15 @@ static int sample_posterior_impl(gpcsd_ctx *c, const PredCall &q, int nsamples, 
                "(ntstar + nt) exceeds the eigensolver's capacity of %d rows (GPCSD_MAX_EIG_N)", ns_l, ntt_l, GPCSD_MAX_EIG_N);
     const int ns = (int)ns_l, ntt = (int)ntt_l;
     // doubles of scratch per pseudo-trial: Xi and Xi Ft^T; E, eps, the residual, W and Bm; S; the prior block and the update
-    const size_t per = 2 * (size_t)ns * ntt + 5 * (size_t)nx * nt + (size_t)nz * nt + 2 * (size_t)nz * ntstar;
+    const size_t per = 2 * (size_t)ns * ntt + 5 * (size_t)nx * nt + (size_t)nz * nt + 2 * (size_t)nz * ntstar + (sink ? sink->per_extra : 0);
     long chunk = (long)std::max<size_t>(1, sample_scratch_budget() / (per * sizeof(double)));
     chunk = std::min(chunk, (GPCSD_MAX_GEMM_LD_KMAJOR - 1) / ntt);       // rows of chunk * nt (or ntstar) doubles are flat GEMM operands
     chunk = std::min(chunk, ((1L << 31) - 1) / std::max(ns, nz));        // chunk * ns rows of Xi, (z, pseudo-trial) columns
     chunk = std::min(chunk, 65535L);                                      // one batch entry per pseudo-trial
     chunk = std::min(chunk, P);
     GP_REQUIRE(chunk >= 1, GPCSD_ERR_CAPACITY, "sample_posterior: one pseudo-trial alone exceeds the capacity of one operand row");
+    if (sink && sink->prelude)
+        if (int rc = sink->prelude()) return rc;
     PostFront f;                                   // (the trials are read chunk by chunk below, as residuals)
     if (int rc = posterior_front(c, q, FRONT_DRAIN, f)) return rc;
     EigState &e = f.e;
@@ -141,8 +152,10 @@ static int sample_posterior_impl(gpcsd_ctx *c, const PredCall &q, int nsamples, 
     double *Sm = c->buf<double>("pred_S", cn * nz * nt);
     double *fp = c->buf<double>("sp_prior", cn * nz * ntstar), *upd = c->buf<double>("sp_upd", cn * nz * ntstar);
     double *out[2] = {nullptr, nullptr};
+    const bool keep = !sink || sink->keep_draws;
     for (int w = 0; w < 2; ++w)
-        if (type & (w + 1)) out[w] = c->buf<double>(w ? "post_sample_lfp" : "post_sample_csd", (size_t)nz * ntstar * P);
+        if (keep && (type & (w + 1))) out[w] = c->buf<double>(w ? "post_sample_lfp" : "post_sample_csd", (size_t)nz * ntstar * P);
+    double *draw = keep ? nullptr : c->buf<double>("feat_draw", cn * nz * ntstar);       // one chunk of one quantity
     const unsigned long long pg0 = (unsigned long long)c->trial_offset * (unsigned long long)S;     // first global pseudo-trial
     for (long p0 = 0; p0 < P; p0 += chunk) {
         const int np = (int)std::min(chunk, P - p0);
@@ -185,7 +198,10 @@ static int sample_posterior_impl(gpcsd_ctx *c, const PredCall &q, int nsamples, 
             g4.prof_name = "gemm_sample_spatial";
             gemm_f64(c, g4, s);
             pred_mean_tail(c, f, q, which, np, Sm, upd, nullptr, 0);     // upd[z][j][q] = P (the residuals), the components summed
-            k_sample_combine(c, upd, fp, out[which - 1], nz, ntstar, np, P, p0, s);     // the one add pass: + f_prior, into (z, t*, p)
+            // the one add pass: + f_prior, into (z, t*, p)
+            if (keep) k_sample_combine(c, upd, fp, out[which - 1], nz, ntstar, np, P, p0, s);
+            else k_sample_combine(c, upd, fp, draw, nz, ntstar, np, np, 0, s);
+            if (sink) sink->consume(which, keep ? out[which - 1] + p0 : draw, keep ? P : (long)np, p0, np);
         }
     }
     const int rc = finish_call(c, e, nullptr, 0);      // (waits for everything queued above)

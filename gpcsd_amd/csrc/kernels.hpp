@@ -359,6 +359,35 @@ void k_eig_factor(gpcsd_ctx *c, const double *Q, const double *w, int nw, const 
 void k_sample_combine(gpcsd_ctx *c, const double *upd, const double *prior, double *out, int nz, int nts, int np, long P, long p0,
                       hipStream_t s);
 
+// ---------------------------------------------------------------- region features of a field (features.hip)
+// The label map as lists, on the device: idx the flat indices i * nts + k of every labelled point, region after region and in
+// row-major order inside a region; slice sl is entries [slice_beg[sl], + slice_cnt[sl]) of it, at most FEAT_SLICE of one region;
+// region j (0-based) owns slices [reg_slice[j], reg_slice[j + 1]).  ptau / pz0 / pz1: the coordinates of entry n (k_feat_coords).
+constexpr int FEAT_SLICE = 256;
+struct FeatPlan {
+    int J = 0, nslice = 0, npts = 0;
+    const int *idx = nullptr, *slice_beg = nullptr, *slice_cnt = nullptr, *reg_slice = nullptr;
+    const double *ptau = nullptr, *pz0 = nullptr, *pz1 = nullptr;
+};
+// feat[j][slot][col0 + p] (J, GPCSD_NFEAT, ldf) of the columns p < ncol of F[point][p] (row length ld), slots as gpcsd_region_features
+// documents them.  mean (points, R) and isd (points), both or neither: slot 9 = max |F - mean[.][(col0 + p) / S]| isd, NaN without.
+// part: scratch of nslice * GPCSD_NFEAT * ncol doubles.  Fixed order, no atomics; a column does not depend on the others.
+struct FeatDesc {
+    const double *F = nullptr;
+    long ld = 0;
+    int ncol = 0;
+    long col0 = 0;
+    const double *mean = nullptr, *isd = nullptr;
+    int R = 0, S = 1;
+    double *part = nullptr, *feat = nullptr;
+    long ldf = 0;
+};
+void k_region_features(gpcsd_ctx *c, const FeatPlan &pl, const FeatDesc &d, hipStream_t s);
+void k_feat_coords(gpcsd_ctx *c, const int *idx, int npts, int nts, const double *tau, const double *zeta, int dim, double *ptau,
+                   double *pz0, double *pz1, hipStream_t s);
+// isd = 1 / sqrt(var) where var > floor * max(var), 0 elsewhere; vmax: one double of scratch
+void k_feat_isd(gpcsd_ctx *c, const double *var, long n, double floor, double *vmax, double *isd, hipStream_t s);
+
 // ---------------------------------------------------------------- eigensolver (eigh.hip)
 // Symmetric eigendecomposition of A (n,n) on device.  evals ascending; evecs (n,n) row-major with
 // eigenvectors in COLUMNS (numpy.linalg.eigh convention).  A is destroyed.  status: device int (0 ok).

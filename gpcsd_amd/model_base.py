@@ -1361,6 +1361,49 @@ class GPCSDModel:
         z2, tstar, code, sh = self._sample_posterior_args(z, tstar, type, nsamples)
         return self._sample_posterior_call(z2, tstar, code, sh, int(nsamples), int(seed), None, None, resident)
 
+    def sample_features(self, z, tstar, labels, nsamples=1, type="csd", seed=1, band=False, return_draws=False, resident=False,
+                        floor=1e-10):
+        """Posterior distributions of NONLINEAR features of the CSD and/or LFP field over labelled regions of the (z, t*) plane: the
+        draws of `sample_posterior(z, tstar, nsamples, type, seed)` reduced on the device, chunk by chunk inside the sampler, so that
+        nothing but the answer grows with `nsamples` -- a latency interval or a simultaneous band takes hundreds of draws per trial,
+        whose fields would be gigabytes.  labels: integer map (nz, ntstar), 0 the background, 1..J the regions (J = labels.max()).
+        Returns (csd_feat, lfp_feat), None for the part not requested: the dicts of `utility_functions.region_features` with arrays
+        over (J, ntrials, nsamples) -- max, min, sum, abs_sum, argmax, argmin, peak_time, trough_time, com_time, com_site.
+
+        band=True adds "supdev": sup over the region of |draw - mean| / sd with the mean of `predict_at` and the variance of
+        `predict_var` at the same sites and times, formed inside the call (`csd_pred`, `csd_var`, ... and their device buffers are
+        left alone); sd counts where var > floor * max(var), other points drop out.  `utility_functions.simultaneous_band(supdev)`
+        is then the half-width of a simultaneous band mean +- q sd over each region.
+        return_draws=True also keeps the draws and returns (csd_feat, lfp_feat, csd, lfp) with the draws as `sample_posterior`
+        returns them; the features are the same bits either way.  resident=True returns the raw slots as zero-copy device views
+        (J, NFEAT, ntrials, nsamples) instead of dicts (`utility_functions.features_from_slots`), and device views of the draws.
+        Validation, seeds, trial sharding (each rank returns its block of trials) and what is not supported are those of
+        `sample_posterior`.  No reference counterpart (the centre of mass as auditory_lfp/fit_mean_function.py:350-353 takes it of
+        one field on the host)."""
+        from .utility_functions import _region_labels, features_from_slots
+        z2, tstar, code, sh = self._sample_posterior_args(z, tstar, type, nsamples)
+        labels, J = _region_labels(labels, z2.shape[0], tstar.size)
+        if band and not 0.0 <= float(floor) < 1.0:
+            raise ValueError("floor must lie in [0, 1)")
+        nsamples = int(nsamples)
+        ctx = self._sync_device()
+        hp, _keep = self._hparams(0.0)                     # no jitter, as predict
+        R_local = self._local_lfp().shape[2]
+        ctx.set_trial_offset(0 if sh is None else sh.local_slice(np.atleast_3d(self.lfp).shape[2]).start or 0)
+        res = ctx.sample_features(hp, z2, tstar, code, nsamples, int(seed), R_local, labels, J, band=band, floor=floor,
+                                  keep_draws=return_draws, resident=resident)
+        feats = []
+        for name in ("csd", "lfp"):
+            f = res.get("feat_" + name)
+            if f is not None and resident:
+                f = _hip.DeviceArray(f.ptr, (J, _hip.NFEAT, R_local, nsamples), ctx, f.name)
+            elif f is not None:
+                f = features_from_slots(f, (R_local, nsamples), tstar.reshape(-1).astype(np.float64), np.asarray(z2, dtype=np.float64), band)
+            feats.append(f)
+        if return_draws:
+            return feats[0], feats[1], res.get("csd"), res.get("lfp")
+        return feats[0], feats[1]
+
     def _sample_posterior_from_normals(self, z, tstar, type, xi, eps):
         """The affine map normals -> draws for host-supplied standard normals: xi (ntrials, nsamples, ns, ntt) with rows
         [CSD(z) if asked; LFP(z) if asked; LFP(x)] and columns [t*; t], eps (ntrials, nsamples, nx, nt).  For tests."""

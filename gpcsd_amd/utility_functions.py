@@ -8,7 +8,10 @@ launches (csrc/phase.hip); torus_graph, the conditional phase coupling those scr
 spectral_operator, power_spectrum, cross_spectrum, spectrum_from_sums: the periodogram those scripts take of every prediction, its
 mean over the trials and the coherence of all site pairs (csrc/spectrum.hip); trial_shift_objective: the objective of the per-trial
 shift fits those scripts run (auditory_lfp/fit_mean_function.py:306-321) with its analytic gradient (csrc/shift.hip);
-roi_weights: box averages and contrasts over (z, t*) as the dense weights of predict_functionals (host only)."""
+roi_weights: box averages and contrasts over (z, t*) as the dense weights of predict_functionals (host only); region_features,
+features_from_slots, simultaneous_band: extrema, their place and time, centres of mass (auditory_lfp/fit_mean_function.py:350-353
+takes them of one segmented field on the host) and standardised suprema over labelled regions, per column of a field
+(csrc/features.hip)."""
 import numpy as np
 
 from . import _hip
@@ -123,6 +126,113 @@ def band_phase(x, A, want=("phase",), resident=False, ctx=None):
         raise ValueError("resident=True needs a device input")
     res = (ctx or _hip.default_context()).analytic(np.asarray(x, dtype=np.float64).reshape(nz, n, M), A, want)
     return {k: v.reshape(out_shape) for k, v in res.items()}
+
+
+def _region_labels(labels, nz, n):
+    """The label map of region_features / sample_features as int32 (nz, n) and the number of regions J = max(labels.max(), 1);
+    ValueError on another shape or a negative label, GPCSDCapacityError beyond _hip.MAX_REGIONS.  No device call."""
+    labels = np.asarray(labels)
+    if labels.shape != (nz, n):
+        raise ValueError("labels must have shape (%d, %d), not %s" % (nz, n, labels.shape))
+    if not np.issubdtype(labels.dtype, np.integer) and not np.array_equal(labels, np.floor(labels)):
+        raise ValueError("labels must be integers: 0 for the background, 1..J for the regions")
+    if labels.size and labels.min() < 0:
+        raise ValueError("a label is out of range: labels are 0 for the background and 1..J for the regions, not %d" % labels.min())
+    J = max(int(labels.max()) if labels.size else 0, 1)
+    if J > _hip.MAX_REGIONS:
+        raise _hip.GPCSDCapacityError("%d regions; at most %d (GPCSD_MAX_REGIONS)" % (J, _hip.MAX_REGIONS))
+    return np.ascontiguousarray(labels, dtype=np.int32), J
+
+
+def _region_coordinates(tstar, z, nz, n):
+    tstar = np.arange(n, dtype=np.float64) if tstar is None else np.asarray(tstar, dtype=np.float64).reshape(-1)
+    z = np.arange(nz, dtype=np.float64) if z is None else np.asarray(z, dtype=np.float64)
+    z = z.reshape(-1, 1) if z.ndim == 1 else z
+    if tstar.size != n or z.ndim != 2 or z.shape[0] != nz or z.shape[1] not in (1, 2):
+        raise ValueError("tstar must hold %d times and z (%d,) or (%d, 1 or 2) sites" % (n, nz, nz))
+    return tstar, z
+
+
+def features_from_slots(feat, tail, tstar, z, band):
+    """The dict region_features returns from the raw slots feat (J, NFEAT, M) of the library (include/gpcsd_hip.h lists them), the
+    columns reshaped to `tail`; tstar (n,) and z (nz, dim) are the coordinates the call was given."""
+    feat = np.asarray(feat)
+    J, n = feat.shape[0], tstar.size
+    f = feat.reshape((J, _hip.NFEAT) + tuple(tail))
+    out = {"slots": f, "max": f[:, 0], "min": f[:, 2], "sum": f[:, 4], "abs_sum": f[:, 5]}
+    for name, when, slot in (("argmax", "peak_time", 1), ("argmin", "trough_time", 3)):
+        flat = f[:, slot].astype(np.int64)
+        empty = flat < 0
+        site, time = np.where(empty, -1, flat // n), np.where(empty, -1, flat % n)
+        out[name] = np.stack([site, time], axis=-1)
+        out[when] = np.where(empty, np.nan, tstar[np.where(empty, 0, time)])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        none = f[:, 5] == 0
+        out["com_time"] = np.where(none, np.nan, f[:, 6] / f[:, 5])
+        out["com_site"] = np.stack([np.where(none, np.nan, f[:, 7 + k] / f[:, 5]) for k in range(z.shape[1])], axis=-1)
+    if band:
+        out["supdev"] = f[:, 9]
+    return out
+
+
+def region_features(x, labels, tstar=None, z=None, mean=None, isd=None, resident=False, ctx=None):
+    """Nonlinear summaries of a field over labelled regions of the (z, t) plane, for every column: x is (nz, n, M) or (nz, n, R, S) --
+    a NumPy array, or a `_hip.DeviceArray` such as a resident prediction or resident posterior draws, read where it lies --, labels
+    an integer map (nz, n) with 0 for the background and 1..J for the regions (J = labels.max(); e.g. a watershed segmentation of
+    the evoked prediction), tstar (n,) and z (nz,) or (nz, dim) the coordinates (default: the indices).  Returns a dict of arrays
+    shaped (J,) + x.shape[2:]:
+
+      max, min, sum, abs_sum     over the region's points
+      argmax, argmin             integer (..., 2) = (site index, time index) of the FIRST occurrence in row-major (z, t) order;
+                                 -1 for a region without a point
+      peak_time, trough_time     tstar at those indices (NaN for a region without a point)
+      com_time, com_site         centre of mass of |x|: sum |x| t / sum |x|, and (..., dim) likewise in z; NaN where abs_sum == 0
+      supdev                     with mean (nz, n, R) and isd (nz, n): max over the region of |x - mean| isd, the trial of a column
+                                 being its index over x.shape[2:] divided by S (-inf for a region without a point)
+      slots                      the raw values of the library, (J, NFEAT) + x.shape[2:], of which the entries above are views or
+                                 quotients (include/gpcsd_hip.h lists them): the sums |x| t and |x| z before the division
+
+    One pass over the field on the device (csrc/features.hip); sums in a fixed order that depends on the labels alone, so the same
+    call returns the same bits and a column's values do not depend on which other columns are passed with it.  NaN inputs are not
+    supported.  resident=True (device input only) returns {"feat": zero-copy view (J, NFEAT) + x.shape[2:] of the library's
+    "feat_out"} -- the raw slots, which `features_from_slots` turns into the dict above.  ctx as in band_phase.  The centre of mass
+    is what the reference's analysis takes of each segmented region of one field on the host (scipy.ndimage.center_of_mass,
+    auditory_lfp/fit_mean_function.py:350-353); as a routine over columns it has no reference counterpart."""
+    shape = tuple(int(v) for v in x.shape)
+    if len(shape) not in (3, 4):
+        raise ValueError("x must be (nz, n, M) or (nz, n, R, S)")
+    nz, n = shape[:2]
+    M = int(np.prod(shape[2:]))
+    S = shape[3] if len(shape) == 4 else 1
+    labels, J = _region_labels(labels, nz, n)
+    tstar, z = _region_coordinates(tstar, z, nz, n)
+    if (mean is None) != (isd is None):
+        raise ValueError("give both mean and isd, or neither")
+    if mean is not None and len(shape) == 3:
+        S = 1 if np.ndim(mean) != 3 or np.shape(mean)[2] == 0 or M % np.shape(mean)[2] else M // np.shape(mean)[2]
+    if isinstance(x, _hip.DeviceArray):
+        if x.base is None:
+            raise ValueError("region_features: the device array is not a view of a named buffer of the library")
+        ctx = x._owner
+        view = ctx.region_features_resident(x.base[0], x.base[1], (nz, n, M), labels, J, tstar, z, mean, isd, S)
+        if resident:
+            return {"feat": _hip.DeviceArray(view.ptr, (J, _hip.NFEAT) + shape[2:], ctx, view.name)}
+        feat = ctx.fetch(view.name, view.shape)
+    else:
+        if resident:
+            raise ValueError("resident=True needs a device input")
+        feat = (ctx or _hip.default_context()).region_features(np.asarray(x, dtype=np.float64).reshape(nz, n, M), labels, J, tstar, z,
+                                                                mean, isd, S)
+    return features_from_slots(feat, shape[2:], tstar, z, mean is not None)
+
+
+def simultaneous_band(supdev, level=0.95):
+    """The half-width q, in posterior standard deviations, of a simultaneous band over each region: the `level` quantile over the
+    draws (last axis) of supdev (J, ntrials, nsamples) as region_features / sample_features return it.  mean +- q sd then covers the
+    whole region with posterior probability `level` (up to the Monte-Carlo error of the quantile).  Host NumPy."""
+    if not 0.0 < float(level) < 1.0:
+        raise ValueError("level must lie in (0, 1)")
+    return np.quantile(np.asarray(supdev, dtype=np.float64), float(level), axis=-1)
 
 
 def plv_from_sums(sums, ntrials):

@@ -54,7 +54,12 @@ extern "C" {
 /*   GPCSD_MAX_SHIFT_NSEG      shifted components of gpcsd_shift_plan (its gradient kernel keeps one partial sum per component in
  *                           registers; the reference's data has 10-20 per probe)                                                */
 #define GPCSD_MAX_SHIFT_NSEG      32
+/*   GPCSD_MAX_REGIONS         labelled regions J of gpcsd_region_features / gpcsd_sample_features (one row of workgroups per region
+ *                           in the pass that folds a region's partial results)                                                   */
+#define GPCSD_MAX_REGIONS         4096
 #define GPCSD_ERR_CAPACITY      (-7)
+/* values per region and column of gpcsd_region_features / gpcsd_sample_features */
+#define GPCSD_NFEAT             10
 
 #define GPCSD_PRED_CSD  1
 #define GPCSD_PRED_LFP  2
@@ -574,6 +579,61 @@ int gpcsd_sample_posterior(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double
 int gpcsd_sample_posterior_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double *z, int nz,
                                     const double *tstar, int ntstar, int type, int nsamples, unsigned long long seed,
                                     const double *normals_xi, const double *normals_eps);
+/* REGION FEATURES of a field x (nz, nts, M), C order, the column m innermost -- a prediction (M = ntrials) or posterior draws
+ * (M = ntrials * nsamples, gpcsd_sample_posterior's layout): per labelled region of the (z, t) plane and per column the extrema, where
+ * and when they occur, the sums that give the centre of mass, and the largest standardised deviation from a mean.  NO REFERENCE
+ * COUNTERPART as a routine: the reference's analysis segments ONE evoked field into labelled regions on the host and takes
+ * scipy.ndimage.center_of_mass of each (auditory_lfp/fit_mean_function.py:350-353); these are the same reductions for every column,
+ * taken where the field lies.  labels (nz, nts) int32 with values 0..J, 0 the background (ignored); tau (nts) and zeta (nz, dim),
+ * dim 1 or 2, the coordinates; mean (nz, nts, R) and isd (nz, nts), both or neither, with M = R * S and column m of trial m / S.
+ * feat (J, GPCSD_NFEAT, M), for region j = 1..J (row j - 1) and column m, over the region's points (i, k):
+ *   slot 0, 1   max of x and the flat index i * nts + k of its FIRST occurrence in row-major (z, t) order (a double, exact)
+ *   slot 2, 3   min of x and the flat index of its first occurrence
+ *   slot 4, 5   sum x, sum |x|
+ *   slot 6      sum |x| tau[k]
+ *   slot 7, 8   sum |x| zeta[i][0], sum |x| zeta[i][1] (0 when dim = 1)
+ *   slot 9      max |x - mean[i][k][m / S]| isd[i][k]; NaN when mean / isd are NULL
+ * A region without a point gives -inf, -1, +inf, -1, zeros, and -inf in slot 9 when it is asked for.  NaN inputs are NOT supported
+ * and nothing checks for them.  Sums are taken in a fixed order that depends on the label map alone, without atomics: the same call
+ * returns the same bits, and a column's result does not depend on which other columns are in the call.  Extrema are replaced on
+ * strict comparisons in point order.  One upload, three launches, one download.
+ * rc -3: NULL or empty arguments, J < 1, a label outside [0, J], mean without isd, R * S != M; GPCSD_ERR_CAPACITY (before anything
+ * is read on the device): J > GPCSD_MAX_REGIONS, nz * nts >= 2^31, J * GPCSD_NFEAT * M >= 2^31, M >= 64 * 65535. */
+int gpcsd_region_features(gpcsd_ctx *ctx, const double *x, int nz, int nts, long M, const int *labels, int J, const double *tau,
+                          const double *zeta, int dim, const double *mean, const double *isd, int R, int S, double *feat);
+/* Same computation (no reference counterpart) on a named device buffer from `src_offset` doubles on (as gpcsd_analytic_resident
+ * takes its source), read as (nz, nts, M); the features are left in "feat_out" (J * GPCSD_NFEAT * M doubles).  rc -2: no such
+ * buffer; -3 also when the buffer is too small or is "feat_out" itself. */
+int gpcsd_region_features_resident(gpcsd_ctx *ctx, const char *src_name, long src_offset, int nz, int nts, long M, const int *labels,
+                                   int J, const double *tau, const double *zeta, int dim, const double *mean, const double *isd,
+                                   int R, int S);
+/* The region features of gpcsd_sample_posterior's draws, reduced chunk by chunk INSIDE the sampler (no reference counterpart; the
+ * centre of mass as auditory_lfp/fit_mean_function.py:350-353 takes it of one field): arguments, model, normals and chunking of
+ * gpcsd_sample_posterior, then labels (nz, ntstar) and J as gpcsd_region_features, tau = tstar and zeta = z.  feat_csd / feat_lfp
+ * (J, GPCSD_NFEAT, ntrials * nsamples), column p = r * nsamples + s; either may be NULL.  After the combine pass of a chunk the
+ * features of its columns are written to columns [p0, p0 + np) of the result, so nothing but the result grows with nsamples:
+ * with keep_draws = 0 a chunk's draws live in a chunk-sized scratch and "post_sample_csd" / "post_sample_lfp" are neither allocated
+ * nor touched (csd and lfp must then be NULL, rc -3); with keep_draws != 0 the draws are kept and returned as
+ * gpcsd_sample_posterior returns them.  The chunk length counts that scratch either way: both settings form the same draws and so
+ * the same features, bit for bit (a chunk may be shorter than gpcsd_sample_posterior's own).
+ * with_band != 0 fills slot 9 with the supremum over the region of |draw - mean| / sd: the call first forms the mean of
+ * gpcsd_predict_at and the variance of gpcsd_predict_var at the same sites and times, through those calls' internals, into buffers of
+ * its own ("feat_mean_csd" / "feat_mean_lfp" (nz, ntstar, ntrials), "feat_var_*" and "feat_isd_*" (nz, ntstar)): "pred_out_*" and
+ * "pred_var_*" are not touched.  1 / sd = 1 / sqrt(var) where var > floor * max(var), 0 elsewhere (floor in [0, 1), 1e-10 by
+ * convention; points below it drop out of the supremum).  The quantile over the draws of slot 9 is the half-width, in standard
+ * deviations, of a simultaneous band over the region.
+ * rc -3: as gpcsd_sample_posterior, J < 1, a label outside [0, J], a floor outside [0, 1); GPCSD_ERR_CAPACITY: as
+ * gpcsd_sample_posterior and gpcsd_region_features with M = ntrials * nsamples, with_band also as gpcsd_predict_at; everything is
+ * checked before any device work. */
+int gpcsd_sample_features(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar, int type,
+                          int nsamples, unsigned long long seed, const double *normals_xi, const double *normals_eps,
+                          const int *labels, int J, int with_band, double floor, int keep_draws, double *feat_csd, double *feat_lfp,
+                          double *csd, double *lfp);
+/* Same computation (no reference counterpart), the features left in "feat_csd" / "feat_lfp" and, with keep_draws != 0, the draws
+ * in "post_sample_csd" / "post_sample_lfp". */
+int gpcsd_sample_features_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const double *z, int nz, const double *tstar, int ntstar,
+                                   int type, int nsamples, unsigned long long seed, const double *normals_xi,
+                                   const double *normals_eps, const int *labels, int J, int with_band, double floor, int keep_draws);
 /* Posterior mean and covariance of J LINEAR FUNCTIONALS <W_j, f> = sum_{z,s} W_j[z, s] f(z, t*_s) of the CSD / LFP field at the sites
  * z and times tstar of gpcsd_predict_at -- a layer and window average, a sink-minus-source contrast, a component's amplitude -- of the
  * model whose mean that call returns (no jitter; a per-electrode noise list on the eigen-index; the LFP is the noise-free potential).
