@@ -93,6 +93,17 @@ class DebugGemmArgs(ctypes.Structure):
                  ("dyn", ctypes.POINTER(ctypes.c_int)), ("nDyn", ctypes.c_long), ("quad_out", _c_double_p), ("nQuad", ctypes.c_long)])
 
 
+class DebugGradArgs(ctypes.Structure):
+    """struct gpcsd_debug_grad_args"""
+    _fields_ = [("op", ctypes.c_int), ("B", ctypes.c_int), ("table", ctypes.c_int), ("n", ctypes.c_int * 4), ("l", ctypes.c_long * 4),
+                ("s", ctypes.c_double * 4), ("hp", ctypes.POINTER(HParams)), ("in_", _c_double_p * 6), ("nin", ctypes.c_long * 6),
+                ("out", _c_double_p * 4), ("nout", ctypes.c_long * 4)]
+
+
+# op of gpcsd_debug_grad_op (include/gpcsd_hip.h) -> (inputs, outputs)
+GRAD_OPS = {"temporal_grad": 0, "frob_inner": 1, "kgl_grad": 2, "frob_pair": 3, "fwdR_grad": 4, "D_sums": 5, "batch_reduce": 6,
+            "siglist_eigvec_term": 7, "rowgroup_sumsq": 8, "per_trial_quad": 9}
+
 EPI_STORE, EPI_DIV_D, EPI_QUAD, EPI_ACCUM, EPI_GRAD, EPI_DUAL_INIT, EPI_SUB = 0, 1, 2, 3, 4, 6, 7      # enum Epi (csrc/kernels.hpp)
 
 
@@ -145,6 +156,7 @@ SIGNATURES = {
     "gpcsd_eigh_psd": (_I, [_P, _DP, _I, _DP, _DP]),
     "gpcsd_eigh_batch": (_I, [_P, _DP, _I, _I, _DP, _DP, ctypes.POINTER(_I)]),
     "gpcsd_debug_gemm": (_I, [_P, ctypes.POINTER(DebugGemmArgs)]),
+    "gpcsd_debug_grad_op": (_I, [_P, ctypes.POINTER(DebugGradArgs)]),
     "gpcsd_eig_D": (_I, [_P, _DP, _I, _DP, _I, _DP, _I, _DP, _DP, _DP]),
     "gpcsd_whitened_quad": (_I, [_P, _DP, _I, _DP, _I, _DP, _DP, _I, _DP]),
     "gpcsd_shift_plan": (_I, [_P, _DP, _I, _DP, _I, _DP, _DP, _I, _DP, _I, _DP]),
@@ -788,6 +800,41 @@ class Context:
             a.nDyn = keep["dyn"].size
         self._check(self._lib.gpcsd_debug_gemm(self._h, ctypes.byref(a)))
         return {"C": keep["C"], "C2": keep["C2"], "C3": keep["C3"], "quad": keep["quad_out"]}
+
+    def debug_grad_op(self, op, inputs, out_lens, n=(), l=(), s=(), B=1, hp=None, table=False):
+        """One launcher of the analytic gradient's contraction kernels (csrc/grad.hip) on its own (gpcsd_debug_grad_op; the table of
+        operations is in include/gpcsd_hip.h).  op: a name in GRAD_OPS; inputs: up to six arrays, uploaded flat exactly as given
+        (None for one the op does not read); out_lens: the lengths of the op's outputs; n, l, s: its int, long and double
+        arguments (l is (..., s_out) where the sets' outputs are s_out apart); hp: an HParamsBatch of B sets, by value (B = 1)
+        or as a device table.  Returns the list of output arrays, flat; the inputs are not written."""
+        a = DebugGradArgs()
+        a.op, a.B, a.table = GRAD_OPS[op], int(B), int(bool(table))
+        if len(inputs) > 6 or len(out_lens) > 4 or len(n) > 4 or len(l) > 4 or len(s) > 4:
+            raise ValueError("debug_grad_op: too many operands")
+        for k, v in enumerate(n):
+            a.n[k] = int(v)
+        for k, v in enumerate(l):
+            a.l[k] = int(v)
+        for k, v in enumerate(s):
+            a.s[k] = float(v)
+        if hp is not None:
+            if len(hp) < (int(B) if table else 1):
+                raise ValueError("debug_grad_op: %d hyper-parameter sets for B = %d" % (len(hp), B))
+            a.hp = hp.pointer()
+        keep = []
+        for k, x in enumerate(inputs):
+            if x is None:
+                continue
+            x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+            keep.append(x)
+            a.in_[k] = _ptr(x)
+            a.nin[k] = x.size
+        outs = [np.empty(max(int(m), 0)) for m in out_lens]
+        for k, o in enumerate(outs):
+            a.out[k] = _ptr(o)
+            a.nout[k] = int(out_lens[k])
+        self._check(self._lib.gpcsd_debug_grad_op(self._h, ctypes.byref(a)))
+        return outs
 
     def eig_D(self, Ks, Kt, sig2n):
         Ks, Kt = _arr(Ks), _arr(Kt)

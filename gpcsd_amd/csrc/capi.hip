@@ -1422,6 +1422,7 @@ extern "C" int gpcsd_set_time(gpcsd_ctx *c, const double *t, int nt) {
 #include "capi_shift.inl"
 #include "capi_torus.inl"
 #include "capi_grad.inl"
+#include "capi_debug_grad.inl"
 #include "capi_fisher.inl"
 #include "capi_measure.inl"
 #include "capi_dist.inl"

@@ -224,6 +224,41 @@ typedef struct gpcsd_debug_gemm_args {
     long nQuad;
 } gpcsd_debug_gemm_args;
 int gpcsd_debug_gemm(gpcsd_ctx *ctx, gpcsd_debug_gemm_args *args);
+/* Diagnostics for the analytic gradient's contraction kernels (csrc/grad.hip; no reference counterpart: they replace the autograd
+ * tape): ONE of the k_* launchers on the context's main stream, host arrays in and out, nothing else between the caller and the
+ * kernels.  in[k] / out[k] are host arrays with their lengths in doubles in nin[k] / nout[k]; the furthest element the launcher
+ * can address is compared with every length before anything is uploaded.  B: hyper-parameter sets (1 where an op has none);
+ * table != 0: the scalars come from a device table of the B sets in hp (built as the gradient evaluation builds it), else from
+ * hp[0] / s[] by value (then B must be 1).  s_out (l[3]): distance of the sets' outputs in out[0] (the evaluation uses 64).
+ *   op  launcher                n[]                  l[]            s[]            in[]                              out[]
+ *   0   k_temporal_grad         nt                   -, -, -, s_out -              Gt (B nt nt), t (nt)              (B s_out): 2 ncomp each
+ *   1   k_frob_inner            nm                   n2             -              Gt (n2), dK (nm n2)               (nm)
+ *   2   k_kgl_grad              G, ngl2 (0: 1D)      -, -, -, s_out ell1, ell2     M, Kgl (B G G), gx1, gx2          (B s_out): 1 or 2 each
+ *   3   k_frob_pair             -                    n, -, -, s_out -              P, T1, T2 (B n)                   (B s_out): 2 each
+ *   4   k_fwdR_grad             nx, G, ngl2 (0: 1D)  -, -, -, s_out R, eps         S (B nx G), x, gx1, gw1, gx2, gw2 (B s_out): 1 each
+ *   5   k_D_sums                nx, nt               -, -, -, s_out -              D (B nx nt), es (B nx), et (B nt) a (B nx), b (B nt), sum 1/D
+ *                                                                                                                    (B s_out), row sums of 1/D (B nx)
+ *   6   k_batch_reduce          nb, n                stride, s_in,  scale, dscale  in, dvec                          (B s_out) [s_out >= n n]
+ *                                                    s_dvec, s_out
+ *   7   k_siglist_eigvec_term   nx                   -              tiny           Ghs, Ssum (B nx nx), es, sig (B nx)  Ghs updated (B nx nx)
+ *   8   k_rowgroup_sumsq        nrows                rowlen         -              B (nrows rowlen)                  (nrows)
+ *   9   k_per_trial_quad        nx, nb, nt           -              -              alpha (nx nb nt), D (nx nt)       (nb)
+ * Table form of op 0: 2 hp[0].n_temporal values are summed for every set (as in an evaluation, whose sets share it), so it
+ * must be the largest of the sets'.  rc -3: an unknown op, a null or short operand, a non-positive size, n_temporal outside
+ * [1, GPCSD_MAX_TEMPORAL], a kind that is neither SE nor Matern, nm outside [1, 2 GPCSD_MAX_TEMPORAL], B > 1 without a table where
+ * the scalars come by value; nothing has been launched then. */
+typedef struct gpcsd_debug_grad_args {
+    int op, B, table;
+    int n[4];
+    long l[4];
+    double s[4];
+    const gpcsd_hparams *hp;             /* B sets (ops 0, 2, 4 with a table; op 0 always) */
+    const double *in[6];
+    long nin[6];
+    double *out[4];
+    long nout[4];
+} gpcsd_debug_grad_args;
+int gpcsd_debug_grad_op(gpcsd_ctx *ctx, gpcsd_debug_grad_args *args);
 /* comp_eig_D(Ks, Kt, sig2n)            utility_functions.py:44-64 ; Dvec has nx*nt entries */
 int gpcsd_eig_D(gpcsd_ctx *ctx, const double *Ks, int nx, const double *Kt, int nt,
                 const double *sig2n, int n_sig, double *Qs, double *Qt, double *Dvec);
