@@ -158,7 +158,7 @@ class GPCSDTemporalCov:
 
 
 class _StationaryTemporalCov(GPCSDTemporalCov):
-    """Shared constructor of the two stationary kernels (ell ~ InvGamma from the sampling grid, sigma2 ~ HalfNormal)."""
+    """Shared constructor of the stationary kernels (ell ~ InvGamma from the sampling grid, sigma2 ~ HalfNormal)."""
     kind = None
     _sigma2_min = 1e-8
 
@@ -190,7 +190,7 @@ class _StationaryTemporalCov(GPCSDTemporalCov):
         from a temporal covariance the library does not evaluate itself.  Any GPCSDTemporalCov subclass with a `compute_Kt` may
         be put in a model (the reference traces it with autograd, covariances.py:235-238, gpcsd1d.py:211); one that also offers
         `compute_dKt(name)` keeps the fit at one device evaluation per optimiser step instead of 2p + 1 (central differences).
-        Host NumPy: this is the contract's default implementation for the two stationary kernels, used when they sit next to a
+        Host NumPy: this is the contract's default implementation for the stationary kernels, used when they sit next to a
         user-defined component (alone, the library differentiates them on the device)."""
         ts = np.asarray(self.t, dtype=np.float64).reshape(-1)
         d = ts[:, None] - ts[None, :]
@@ -198,10 +198,22 @@ class _StationaryTemporalCov(GPCSDTemporalCov):
         if self.kind == _hip.KIND_SE:
             k = np.exp(-0.5 * np.square(d) / (ell * ell))
             dk = k * np.square(d) / (ell * ell * ell)
-        else:
+        elif self.kind == _hip.KIND_MATERN:
             ad = np.abs(d)
             k = np.exp(-ad / ell)
             dk = k * ad / (ell * ell)
+        elif self.kind == _hip.KIND_MATERN32:
+            a = np.sqrt(3.0) * np.abs(d) / ell
+            e = np.exp(-a)
+            k = (1.0 + a) * e
+            dk = a * a * e / ell
+        elif self.kind == _hip.KIND_MATERN52:
+            a = np.sqrt(5.0) * np.abs(d) / ell
+            e = np.exp(-a)
+            k = (1.0 + a + a * a / 3.0) * e
+            dk = a * a * (1.0 + a) * e / (3.0 * ell)
+        else:
+            raise ValueError("compute_dKt: unknown temporal kernel kind %r" % (self.kind,))
         if name == "ell":
             return s2 * dk
         if name == "sigma2":
@@ -219,3 +231,17 @@ class GPCSDTemporalCovMatern(_StationaryTemporalCov):
     """sigma2 * exp(-|t-t'| / ell)   (Matern-1/2; reference: covariances.py:274-305; sigma2 lower bound 0)."""
     kind = _hip.KIND_MATERN
     _sigma2_min = 0
+
+
+class GPCSDTemporalCovMatern32(_StationaryTemporalCov):
+    """sigma2 * (1 + a) * exp(-a), a = sqrt(3) |t-t'| / ell   (Matern-3/2: once differentiable sample paths; no reference
+    counterpart, evaluated on the device like the two kernels above)."""
+    kind = _hip.KIND_MATERN32
+    _sigma2_min = 1e-8
+
+
+class GPCSDTemporalCovMatern52(_StationaryTemporalCov):
+    """sigma2 * (1 + a + a^2 / 3) * exp(-a), a = sqrt(5) |t-t'| / ell   (Matern-5/2: twice differentiable sample paths; no
+    reference counterpart, evaluated on the device like the two kernels above)."""
+    kind = _hip.KIND_MATERN52
+    _sigma2_min = 1e-8

@@ -8,6 +8,7 @@
 #include <optional>
 
 #include "kernels.hpp"
+#include "temporal_kernel.hpp"
 #include "jacobi.hpp"
 
 using namespace gpcsd;
@@ -304,7 +305,7 @@ static void spatial_fill(gpcsd_ctx *c, const double *Ks, int nx, long sK, int nr
 
 bool uses_host_kt(const gpcsd_hparams *hp);
 
-// Kt*_c = cov_c.compute_Kt(tstar) (ntstar, nt) of component cc (gpcsd1d.py:277): built on the device for SE / Matern, copied
+// Kt*_c = cov_c.compute_Kt(tstar) (ntstar, nt) of component cc (gpcsd1d.py:277): built on the device for the built-in kinds, copied
 // from the caller's matrices when the temporal covariances are user-defined
 void temporal_cross_gram(gpcsd_ctx *c, const gpcsd_hparams *hp, int cc, const double *dts, int ntstar, const double *t, int nt,
                          double *out, hipStream_t s) {
@@ -327,7 +328,7 @@ void check_hp(gpcsd_ctx *c, const gpcsd_hparams *hp, int nx) {
                "sig2n must have 1 or nx=%d entries (got %d)", nx, hp->n_sig2n);
     for (int i = 0; i < hp->n_temporal; ++i) {
         const int k = hp->kind[i];
-        GP_REQUIRE(k == GPCSD_KIND_SE || k == GPCSD_KIND_MATERN || k == GPCSD_KIND_HOST, -3, "unknown temporal kernel kind %d", k);
+        GP_REQUIRE(temporal_kind_on_device(k) || k == GPCSD_KIND_HOST, -3, "unknown temporal kernel kind %d", k);
         GP_REQUIRE(k != GPCSD_KIND_HOST || c->host_kt_on, -3,
                    "temporal component %d is GPCSD_KIND_HOST but no Gram matrix was supplied (gpcsd_set_host_temporal_gram)", i);
     }

@@ -46,7 +46,7 @@ extern "C" int gpcsd_debug_grad_op(gpcsd_ctx *c, gpcsd_debug_grad_args *a) {
                        b, h.n_temporal, GPCSD_MAX_TEMPORAL);
             GP_REQUIRE(h.n_temporal <= a->hp[0].n_temporal, -3, "debug_grad_op: set %d has more temporal components than set 0", b);
             for (int i = 0; i < h.n_temporal; ++i)
-                GP_REQUIRE(h.kind[i] == GPCSD_KIND_SE || h.kind[i] == GPCSD_KIND_MATERN, -3, "debug_grad_op: set %d, component %d: kind %d",
+                GP_REQUIRE(temporal_kind_on_device(h.kind[i]), -3, "debug_grad_op: set %d, component %d: kind %d",
                            b, i, h.kind[i]);
             GP_REQUIRE(h.sig2n, -3, "debug_grad_op: set %d has no noise variance", b);
         }

@@ -53,7 +53,7 @@ extern "C" int gpcsd_b_fwd_2d(gpcsd_ctx *c, const double *d1, const double *d2, 
 extern "C" int gpcsd_gram_temporal(gpcsd_ctx *c, int kind, const double *t, int n, const double *tp, int m, double ell,
                                    double sigma2, double *out) {
     GP_API_BEGIN(c)
-    GP_REQUIRE(kind == GPCSD_KIND_SE || kind == GPCSD_KIND_MATERN, -3, "unknown temporal kernel kind %d", kind);
+    GP_REQUIRE(temporal_kind_on_device(kind), -3, "unknown temporal kernel kind %d", kind);
     if (n <= 0 || m <= 0) return 0;
     double *dt = c->upload<double>("op_in0", t, n);
     double *dtp = c->upload<double>("op_in1", tp, m);

@@ -28,6 +28,7 @@
 
 #include "devutil.hpp"
 #include "kernels.hpp"
+#include "temporal_kernel.hpp"
 
 namespace gpcsd {
 
@@ -378,15 +379,8 @@ __global__ __launch_bounds__(256) void temporal_dgram_kernel(TemporalSet p, cons
     const int cc = blockIdx.y;
     const double d = t[e / nt] - t[e % nt];
     const double ell = p.ell[cc];
-    double k, dk;                                     // unit-variance kernel and its ell-derivative
-    if (p.kind[cc] == GPCSD_KIND_SE) {
-        k = exp(-0.5 * (d * d) / (ell * ell));
-        dk = k * (d * d) / (ell * ell * ell);
-    } else {
-        const double ad = fabs(d);
-        k = exp(-ad / ell);
-        dk = k * ad / (ell * ell);
-    }
+    double k, dk;                                     // unit-variance kernel and its ell-derivative (temporal_kernel.hpp)
+    temporal_kernel_value_dell<double>(p.kind[cc], d, ell, k, dk);
     out[(2L * cc) * n2 + e] = p.sigma2[cc] * dk;
     out[(2L * cc + 1) * n2 + e] = k;
 }

@@ -8,6 +8,7 @@
 // the deterministic reductions (per-block partials in fixed order, then one block per output value).
 #include "devutil.hpp"
 #include "kernels.hpp"
+#include "temporal_kernel.hpp"
 
 namespace gpcsd {
 
@@ -176,15 +177,8 @@ __global__ __launch_bounds__(256) void temporal_grad_kernel(TGradParams p, const
         for (int cc = 0; cc < GPCSD_MAX_TEMPORAL; ++cc) {
             if (cc < p.ncomp) {
                 const double ell = p.ell[cc];
-                double k, dk;                     // unit-variance kernel and its ell-derivative
-                if (p.kind[cc] == GPCSD_KIND_SE) {
-                    k = exp(-0.5 * (d * d) / (ell * ell));
-                    dk = k * (d * d) / (ell * ell * ell);
-                } else {
-                    const double ad = fabs(d);
-                    k = exp(-ad / ell);
-                    dk = k * ad / (ell * ell);
-                }
+                double k, dk;                     // unit-variance kernel and its ell-derivative (temporal_kernel.hpp)
+                temporal_kernel_value_dell<double>(p.kind[cc], d, ell, k, dk);
                 v[2 * cc] += g * p.sigma2[cc] * dk;
                 v[2 * cc + 1] += g * k;
             }

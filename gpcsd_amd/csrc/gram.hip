@@ -5,6 +5,7 @@
 // reference expressions so results agree to the last few ulps (no fast-math, IEEE div/sqrt).
 #include "devutil.hpp"
 #include "kernels.hpp"
+#include "temporal_kernel.hpp"
 
 namespace gpcsd {
 
@@ -123,11 +124,7 @@ __global__ __launch_bounds__(256) void temporal_gram_kernel(TemporalParams p, co
         T acc = T(0);                                                  // Kt = zeros; Kt = Kt + K_c (gpcsd1d.py:118-120)
         for (int cc = 0; cc < p.ncomp; ++cc) {
             const T ell = T(p.ell[cc]), s2 = T(p.sigma2[cc]);
-            T v;
-            if (p.kind[cc] == GPCSD_KIND_SE)
-                v = s2 * exp(T(-0.5) * (d * d) / (ell * ell));         // covariances.py:270
-            else
-                v = s2 * exp(-sqrt(d * d) / ell);                      // covariances.py:304
+            const T v = s2 * temporal_kernel_value<T>(p.kind[cc], d, ell);   // (wave-uniform switch: temporal_kernel.hpp)
             acc = acc + v;
         }
         out[(long)row * m + col] = (double)acc;
@@ -194,11 +191,7 @@ __device__ __forceinline__ double tset_eval(const P &p, const T ti, const T tj) 
     T acc = T(0);                                                      // Kt = zeros; Kt = Kt + K_c (gpcsd1d.py:118-120)
     for (int cc = 0; cc < p.ncomp; ++cc) {
         const T ell = T(p.ell_of(cc)), s2 = T(p.sigma2_of(cc));
-        T v;
-        if (p.kind[cc] == GPCSD_KIND_SE)
-            v = s2 * exp(T(-0.5) * (d * d) / (ell * ell));             // covariances.py:270
-        else
-            v = s2 * exp(-sqrt(d * d) / ell);                          // covariances.py:304
+        const T v = s2 * temporal_kernel_value<T>(p.kind[cc], d, ell);       // (wave-uniform switch: temporal_kernel.hpp)
         acc = acc + v;
     }
     return (double)acc;
@@ -299,7 +292,7 @@ void k_temporal_fold_fill(gpcsd_ctx *c, const TemporalSet *sets, int nrep, const
     g.status_stride = status_stride;
     g.elem_blocks = ceil_div((long)sy.ns * sy.ns, 256);
     const int zero_blocks = 64;
-    // sums of SE / Matern-1/2 kernels with non-negative variances: positive semi-definite (EigArenaView::psd)
+    // sums of SE / Matern kernels (every GPCSD_KIND_* of the device) with non-negative variances: positive semi-definite (EigArenaView::psd)
     bool nonneg = true;
     for (int r = 0; r < nrep; ++r)
         for (int cc = 0; cc < sets[r].ncomp; ++cc) nonneg = nonneg && sets[r].sigma2[cc] >= 0.0;

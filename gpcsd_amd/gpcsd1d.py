@@ -6,7 +6,8 @@ extract/restore_model_params :84-102, update_lfp :104-111, JITTER :17); the arit
 import numpy as np
 
 from . import _hip
-from .covariances import GPCSD1DSpatialCovSE, GPCSDTemporalCovSE, GPCSDTemporalCovMatern
+from .covariances import GPCSD1DSpatialCovSE, GPCSDTemporalCovSE, GPCSDTemporalCovMatern  # noqa: F401
+from .covariances import GPCSDTemporalCovMatern32, GPCSDTemporalCovMatern52  # noqa: F401
 from .model_base import GPCSDModel
 from .priors import GPCSDInvGammaPrior, GPCSDHalfNormalPrior
 

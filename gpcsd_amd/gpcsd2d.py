@@ -5,7 +5,8 @@ extract/restore_model_params :103-125, update_lfp :127-134, JITTER :16)."""
 import numpy as np
 
 from . import _hip
-from .covariances import GPCSD2DSpatialCovSE, GPCSDTemporalCovSE, GPCSDTemporalCovMatern
+from .covariances import GPCSD2DSpatialCovSE, GPCSDTemporalCovSE, GPCSDTemporalCovMatern  # noqa: F401
+from .covariances import GPCSDTemporalCovMatern32, GPCSDTemporalCovMatern52  # noqa: F401
 from .gpcsd1d import _noise_param
 from .model_base import GPCSDModel
 from .priors import GPCSDInvGammaPrior

@@ -17,6 +17,10 @@ from tqdm import tqdm
 from . import _hip
 from .covariances import GPCSDTemporalCov
 
+# kernels without a reference class of their own: __str__ prints their form beside the class name
+_KIND_FORMS = {_hip.KIND_MATERN32: "Matern-3/2, sigma2 (1 + a) exp(-a), a = sqrt(3) |t-t'| / ell",
+               _hip.KIND_MATERN52: "Matern-5/2, sigma2 (1 + a + a^2/3) exp(-a), a = sqrt(5) |t-t'| / ell"}
+
 
 def _same_array(a, b):
     return a is b or (np.shape(a) == np.shape(b) and np.array_equal(a, b))
@@ -107,13 +111,13 @@ class GPCSDModel:
 
     # ------------------------------------------------------------------ hyper-parameters
     def _temporal_triplets(self):
-        """[(kind, ell, sigma2)] per temporal component.  SE / Matern are evaluated by the library's own Gram builders; any
-        other object with a `compute_Kt` method (the reference accepts those: covariances.py:235-238, gpcsd1d.py:118-120)
-        is marked KIND_HOST and its Gram matrices are evaluated on the host by that method (see `_hparams`)."""
+        """[(kind, ell, sigma2)] per temporal component.  The kinds of _hip.DEVICE_KINDS (SE, Matern-1/2, -3/2, -5/2) are
+        evaluated by the library's own Gram builders; any other object with a `compute_Kt` method (the reference accepts
+        those: covariances.py:235-238, gpcsd1d.py:118-120) is marked KIND_HOST and its Gram matrices are evaluated on the host by that method (see `_hparams`)."""
         out = []
         for tc in self.temporal_cov_list:
             kind = getattr(tc, "kind", None)
-            if isinstance(tc, GPCSDTemporalCov) and kind in (_hip.KIND_SE, _hip.KIND_MATERN):
+            if isinstance(tc, GPCSDTemporalCov) and kind in _hip.DEVICE_KINDS:
                 out.append((kind, tc.params["ell"]["value"], tc.params["sigma2"]["value"]))
             elif callable(getattr(tc, "compute_Kt", None)):
                 out.append((_hip.KIND_HOST, 0.0, 0.0))
@@ -198,6 +202,8 @@ class GPCSDModel:
         s = ""
         for i, tc in enumerate(self.temporal_cov_list):
             s += "Temporal covariance %d class name: %s\n" % (i + 1, type(tc).__name__)
+            if getattr(tc, "kind", None) in _KIND_FORMS:
+                s += "Temporal covariance %d kernel: %s\n" % (i + 1, _KIND_FORMS[tc.kind])
             s += "Temporal covariance %d ell prior: %s\n" % (i + 1, str(tc.params["ell"]["prior"]))
             s += "Temporal covariance %d ell value %0.4g\n" % (i + 1, tc.params["ell"]["value"])
             s += "Temporal covariance %d sigma2 prior: %s\n" % (i + 1, str(tc.params["sigma2"]["prior"]))
@@ -770,8 +776,8 @@ class GPCSDModel:
         if getattr(self, "_sharding", None) is not None:
             raise NotImplementedError(who + ": trial-sharded models are not supported")
         if self._uses_host_kt():
-            raise NotImplementedError(who + ": user-defined temporal covariances are not supported; only GPCSDTemporalCovSE / "
-                                      "GPCSDTemporalCovMatern components are")
+            raise NotImplementedError(who + ": user-defined temporal covariances are not supported; only the library's own "
+                                      "GPCSDTemporalCov* components are")
         mask = np.asarray(mask)
         shape = tuple(np.shape(self.lfp))
         if len(shape) != 3 or mask.shape not in (shape, shape[:2]):
@@ -833,7 +839,7 @@ class GPCSDModel:
         z, z2, tstar, code = self._posterior_request(z, tstar, type)
         if self._uses_host_kt():
             raise NotImplementedError("predict_var: a user-defined temporal covariance has no prior variance k(t*, t*) on the device; "
-                                      "only GPCSDTemporalCovSE / GPCSDTemporalCovMatern components are supported")
+                                      "only the library's own GPCSDTemporalCov* components are supported")
         ctx = self._sync_device()
         hp, _keep = self._hparams(0.0)                     # no jitter, as predict
         C = len(self.temporal_cov_list)
@@ -887,7 +893,7 @@ class GPCSDModel:
             raise ValueError("predict_functionals: W holds non-finite entries")
         if self._uses_host_kt():
             raise NotImplementedError("predict_functionals: a user-defined temporal covariance has no prior covariance k(t*, t*) on the "
-                                      "device; only GPCSDTemporalCovSE / GPCSDTemporalCovMatern components are supported")
+                                      "device; only the library's own GPCSDTemporalCov* components are supported")
         ctx = self._sync_device()
         hp, _keep = self._hparams(0.0)                     # no jitter, as predict
         J, C, R_local = W.shape[0], len(self.temporal_cov_list), self._local_lfp().shape[2]
@@ -1325,7 +1331,7 @@ class GPCSDModel:
             raise ValueError("nsamples must be at least 1")
         if self._uses_host_kt():
             raise NotImplementedError("sample_posterior: a user-defined temporal covariance has no joint Gram over [t*; t] on the device; "
-                                      "only GPCSDTemporalCovSE / GPCSDTemporalCovMatern components are supported")
+                                      "only the library's own GPCSDTemporalCov* components are supported")
         sh = getattr(self, "_sharding", None)
         if sh is not None and getattr(sh, "gather_predictions", False):
             raise NotImplementedError("sample_posterior: gather_predictions does not apply to draws; each rank returns its block of trials")

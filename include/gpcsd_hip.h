@@ -37,6 +37,11 @@ extern "C" {
 #define GPCSD_KIND_MATERN  1   /* covariances.py:291-305 */
 #define GPCSD_KIND_HOST    2   /* user-defined GPCSDTemporalCov subclass (covariances.py:235-238): its Gram matrices are
                                   evaluated by the caller's compute_Kt and handed over with gpcsd_set_host_temporal_gram */
+/* The two kinds between Matern-1/2 (GPCSD_KIND_MATERN) and SE, evaluated on the device like those (no counterpart in the reference;
+ * sigma2 (1 + a) exp(-a), a = sqrt(3) |d| / ell, and sigma2 (1 + a + a^2 / 3) exp(-a), a = sqrt(5) |d| / ell).  Accepted wherever
+ * SE and MATERN are; every other value is rejected with rc -3 before anything is launched. */
+#define GPCSD_KIND_MATERN32 3
+#define GPCSD_KIND_MATERN52 4
 
 /* Capacity limits of this build (no counterpart in the reference, which is bounded by host memory only).  Exceeding one
  * returns GPCSD_ERR_CAPACITY (-7), which the Python layer raises as gpcsd_amd.GPCSDCapacityError -- a RuntimeError, so
@@ -145,7 +150,8 @@ int gpcsd_trad_csd(gpcsd_ctx *ctx, const double *lfp, long n_outer, long n_axis,
 /* b_fwd_2d(delta1, delta2, R, eps, w)   forward_models.py:42-54  (w != NULL -> d1,d2 ignored) */
 int gpcsd_b_fwd_2d(gpcsd_ctx *ctx, const double *d1, const double *d2, const double *w, long n,
                    double R, double eps, double *out);
-/* GPCSDTemporalCov{SE,Matern}.compute_Kt(t, tprime)   covariances.py:257-271 / :291-305; out (n, m) */
+/* GPCSDTemporalCov{SE,Matern,Matern32,Matern52}.compute_Kt(t, tprime)   covariances.py:257-271 / :291-305; out (n, m).
+ * kind: any GPCSD_KIND_* but HOST (rc -3 otherwise). */
 int gpcsd_gram_temporal(gpcsd_ctx *ctx, int kind, const double *t, int n, const double *tp, int m,
                         double ell, double sigma2, double *out);
 /* GPCSD1DSpatialCovSE.compute_Ks        covariances.py:50-56 ; out (nx, nx) */
@@ -245,7 +251,7 @@ int gpcsd_debug_gemm(gpcsd_ctx *ctx, gpcsd_debug_gemm_args *args);
  *   9   k_per_trial_quad        nx, nb, nt           -              -              alpha (nx nb nt), D (nx nt)       (nb)
  * Table form of op 0: 2 hp[0].n_temporal values are summed for every set (as in an evaluation, whose sets share it), so it
  * must be the largest of the sets'.  rc -3: an unknown op, a null or short operand, a non-positive size, n_temporal outside
- * [1, GPCSD_MAX_TEMPORAL], a kind that is neither SE nor Matern, nm outside [1, 2 GPCSD_MAX_TEMPORAL], B > 1 without a table where
+ * [1, GPCSD_MAX_TEMPORAL], a kind the device does not evaluate (GPCSD_KIND_HOST, unknown values), nm outside [1, 2 GPCSD_MAX_TEMPORAL], B > 1 without a table where
  * the scalars come by value; nothing has been launched then. */
 typedef struct gpcsd_debug_grad_args {
     int op, B, table;
