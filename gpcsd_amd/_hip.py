@@ -106,6 +106,19 @@ class DebugGradArgs(ctypes.Structure):
 GRAD_OPS = {"temporal_grad": 0, "frob_inner": 1, "kgl_grad": 2, "frob_pair": 3, "fwdR_grad": 4, "D_sums": 5, "batch_reduce": 6,
             "siglist_eigvec_term": 7, "rowgroup_sumsq": 8, "per_trial_quad": 9}
 
+class DebugFoldArgs(ctypes.Structure):
+    """struct gpcsd_debug_fold_args"""
+    _fields_ = [("op", ctypes.c_int), ("B", ctypes.c_int), ("table", ctypes.c_int), ("list", ctypes.c_int), ("n", ctypes.c_int * 4),
+                ("l", ctypes.c_long * 4), ("s", ctypes.c_double * 4), ("fill", ctypes.c_double), ("hp", ctypes.POINTER(HParams)),
+                ("perm", ctypes.POINTER(ctypes.c_int) * 2), ("nperm", ctypes.c_int * 2), ("in_", _c_double_p * 2),
+                ("nin", ctypes.c_long * 2), ("out", _c_double_p * 5), ("nout", ctypes.c_long * 5),
+                ("status", ctypes.POINTER(ctypes.c_int)), ("nstatus", ctypes.c_int)]
+
+
+# op of gpcsd_debug_fold_op (include/gpcsd_hip.h)
+FOLD_OPS = {"swap_last2": 0, "swap_last2_sum": 1, "sym_fold_rect": 2, "sym_unfold_mat": 3, "fold_lfp": 4, "unfold_swap_sum": 5,
+            "temporal_fold_fill": 6, "psd_fold_fill": 7}
+
 EPI_STORE, EPI_DIV_D, EPI_QUAD, EPI_ACCUM, EPI_GRAD, EPI_DUAL_INIT, EPI_SUB = 0, 1, 2, 3, 4, 6, 7      # enum Epi (csrc/kernels.hpp)
 
 
@@ -159,6 +172,7 @@ SIGNATURES = {
     "gpcsd_eigh_batch": (_I, [_P, _DP, _I, _I, _DP, _DP, ctypes.POINTER(_I)]),
     "gpcsd_debug_gemm": (_I, [_P, ctypes.POINTER(DebugGemmArgs)]),
     "gpcsd_debug_grad_op": (_I, [_P, ctypes.POINTER(DebugGradArgs)]),
+    "gpcsd_debug_fold_op": (_I, [_P, ctypes.POINTER(DebugFoldArgs)]),
     "gpcsd_eig_D": (_I, [_P, _DP, _I, _DP, _I, _DP, _I, _DP, _DP, _DP]),
     "gpcsd_whitened_quad": (_I, [_P, _DP, _I, _DP, _I, _DP, _DP, _I, _DP]),
     "gpcsd_shift_plan": (_I, [_P, _DP, _I, _DP, _I, _DP, _DP, _I, _DP, _I, _DP]),
@@ -837,6 +851,54 @@ class Context:
             a.nout[k] = int(out_lens[k])
         self._check(self._lib.gpcsd_debug_grad_op(self._h, ctypes.byref(a)))
         return outs
+
+    def debug_fold_op(self, op, inputs, out_lens, perms=(), n=(), l=(), s=(), B=1, hp=None, table=False, with_list=False,
+                      fill=0.0, nstatus=0):
+        """One launcher of the folded-basis / relayout kernels (csrc/gram.hip, csrc/eigh.hip) on its own (gpcsd_debug_fold_op; the
+        table of operations is in include/gpcsd_hip.h).  op: a name in FOLD_OPS; inputs: up to two arrays, uploaded flat exactly as
+        given; out_lens: the lengths of the op's outputs, each of which starts as the float64 `fill` and comes back whole; perms: up
+        to two involutions (int arrays); n, l, s: the op's int, long and double arguments; hp: an HParamsBatch of B sets.  Returns
+        the list of output arrays, flat (ops 6 and 7: the int32 status words, nstatus of them, as the last one); the inputs are
+        not written."""
+        a = DebugFoldArgs()
+        a.op, a.B, a.table, a.list, a.fill = FOLD_OPS[op], int(B), int(bool(table)), int(bool(with_list)), float(fill)
+        if len(inputs) > 2 or len(out_lens) > 5 or len(perms) > 2 or len(n) > 4 or len(l) > 4 or len(s) > 4:
+            raise ValueError("debug_fold_op: too many operands")
+        for k, v in enumerate(n):
+            a.n[k] = int(v)
+        for k, v in enumerate(l):
+            a.l[k] = int(v)
+        for k, v in enumerate(s):
+            a.s[k] = float(v)
+        if hp is not None:
+            if len(hp) < int(B):
+                raise ValueError("debug_fold_op: %d hyper-parameter sets for B = %d" % (len(hp), B))
+            a.hp = hp.pointer()
+        keep = []
+        for k, p in enumerate(perms):
+            if p is None:
+                continue
+            p = np.ascontiguousarray(p, dtype=np.int32).reshape(-1)
+            keep.append(p)
+            a.perm[k] = p.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+            a.nperm[k] = p.size
+        for k, x in enumerate(inputs):
+            if x is None:
+                continue
+            x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+            keep.append(x)
+            a.in_[k] = _ptr(x)
+            a.nin[k] = x.size
+        outs = [np.empty(max(int(m), 0)) for m in out_lens]
+        for k, o in enumerate(outs):
+            a.out[k] = _ptr(o)
+            a.nout[k] = int(out_lens[k])
+        status = np.full(max(int(nstatus), 1), -1, dtype=np.int32)
+        if nstatus:
+            a.status = status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+            a.nstatus = int(nstatus)
+        self._check(self._lib.gpcsd_debug_fold_op(self._h, ctypes.byref(a)))
+        return outs + ([status[:int(nstatus)]] if nstatus else [])
 
     def eig_D(self, Ks, Kt, sig2n):
         Ks, Kt = _arr(Ks), _arr(Kt)

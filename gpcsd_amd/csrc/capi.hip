@@ -342,6 +342,34 @@ bool uses_host_kt(const gpcsd_hparams *hp) {
     return false;
 }
 
+// Orbit tables of an involution perm (perm[perm[i]] == i, the caller's to check) of n points, in SymDev's order: tbl = rep_i (ns) |
+// rep_j (ns) | orb (n) | sgn (n) with the pairs in the order of their first members, then the fixed points.  Returns the number of
+// pairs na (ns = n - na).  The identity gives identity_sym's table.
+static int orbit_tables(const std::vector<int> &perm, std::vector<int> &tbl) {
+    const int n = (int)perm.size();
+    int na = 0;
+    for (int i = 0; i < n; ++i)
+        if (perm[i] > i) ++na;
+    const int ns = n - na;
+    tbl.assign((size_t)2 * ns + 2 * n, 0);
+    int *rep_i = tbl.data(), *rep_j = rep_i + ns, *orb = rep_j + ns, *sgn = orb + n;
+    int a = 0;
+    for (int i = 0; i < n; ++i)
+        if (perm[i] > i) {
+            rep_i[a] = i; rep_j[a] = perm[i];
+            orb[i] = a; sgn[i] = 1;
+            orb[perm[i]] = a; sgn[perm[i]] = -1;
+            ++a;
+        }
+    for (int i = 0; i < n; ++i)
+        if (perm[i] == i) {
+            rep_i[a] = i; rep_j[a] = i;
+            orb[i] = a; sgn[i] = 0;
+            ++a;
+        }
+    return na;
+}
+
 // ---- reflection symmetry of a point set (host): find the involution i -> P(i) with pts[P(i)] = 2*centre - pts[i]
 // along the dimensions flagged in `reflect`, and upload its orbit tables.  Returns an empty SymDev if there is none.
 SymDev find_symmetry(gpcsd_ctx *c, const std::string &name, const double *pts, int n, int dim, const double *centre,
@@ -374,23 +402,8 @@ SymDev find_symmetry(gpcsd_ctx *c, const std::string &name, const double *pts, i
         if (perm[i] > i) ++npairs;
     }
     if (npairs == 0) return out;
-    const int ns = n - npairs, na = npairs;
-    std::vector<int> tbl(2 * ns + 2 * n);
-    int *rep_i = tbl.data(), *rep_j = rep_i + ns, *orb = rep_j + ns, *sgn = orb + n;
-    int a = 0;
-    for (int i = 0; i < n; ++i)
-        if (perm[i] > i) {
-            rep_i[a] = i; rep_j[a] = perm[i];
-            orb[i] = a; sgn[i] = 1;
-            orb[perm[i]] = a; sgn[perm[i]] = -1;
-            ++a;
-        }
-    for (int i = 0; i < n; ++i)
-        if (perm[i] == i) {
-            rep_i[a] = i; rep_j[a] = i;
-            orb[i] = a; sgn[i] = 0;
-            ++a;
-        }
+    std::vector<int> tbl;
+    const int na = orbit_tables(perm, tbl), ns = n - na;
     int *d = c->buf<int>(name, tbl.size());
     c->copy_in(d, tbl.data(), tbl.size() * sizeof(int), c->stream);
     GP_HIP(hipStreamSynchronize(c->stream));
@@ -1424,6 +1437,7 @@ extern "C" int gpcsd_set_time(gpcsd_ctx *c, const double *t, int nt) {
 #include "capi_torus.inl"
 #include "capi_grad.inl"
 #include "capi_debug_grad.inl"
+#include "capi_debug_fold.inl"
 #include "capi_fisher.inl"
 #include "capi_measure.inl"
 #include "capi_dist.inl"

@@ -186,8 +186,8 @@ __global__ __launch_bounds__(256) void psd_fold_fill_kernel(PsdFoldFillArgs g) {
         const long nvs = (long)(ns + 64) * ns, nva = (long)(na + 64) * na;
         for (long i = i0; i < nvs; i += stride) Vs[i] = 0.0;
         for (long i = i0; i < nva; i += stride) Va[i] = 0.0;
-        for (long i = i0; i < ns + 64; i += stride) ts[i] = 0.0;
-        for (long i = i0; i < na + 64; i += stride) ta[i] = 0.0;
+        for (long i = i0; i < ns + 64; i += stride) ts[i] = 0.0;           // (tau's n + WY_NB entries; the progress word behind them
+        for (long i = i0; i < na + 64; i += stride) ta[i] = 0.0;           //  belongs to staged temporal chains: eigh_dc.hip, sy_progress_word)
         if (blockIdx.x == g.elem_blocks && threadIdx.x == 0) {
             g.amaxs[rep * g.blks] = m_s;
             g.amaxa[rep * g.blka] = m_a;

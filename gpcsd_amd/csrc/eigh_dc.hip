@@ -87,7 +87,12 @@ struct SytrdProb {
     long blk;             // replica stride of the arena, in doubles
     int pipe;             // the register tail publishes its progress panel by panel (sy_progress_word; whole problems only)
 };
-// the progress word of a problem: behind tau's n + WY_NB entries (the slice has two more; cleared with tau by whoever fills the arena)
+// The progress word of a problem: behind tau's n + WY_NB entries (the slice has two more).  Only a problem whose tail runs with
+// `pipe` writes or is asked for it, and only EighCall::progress sets pipe: the staged TEMPORAL chain (capi.hip: TChain::request)
+// is the one caller that does.  So the fills of the temporal classes clear it with tau -- n + WY_NB + 2 words: the preparation
+// pass below and k_temporal_fold_fill -- while k_psd_fold_fill, which fills the spatial classes alone, clears tau's n + WY_NB
+// entries and leaves the two words behind them as they are: nothing reads them there.  (tests/test_fold_kernels.py asserts both
+// extents; a fill that starts to serve a class with progress words has to clear n + WY_NB + 2.)
 __host__ __device__ inline unsigned *sy_progress_word(const SytrdProb &P) { return reinterpret_cast<unsigned *>(P.tau + P.n + WY_NB); }
 struct SytrdBatch {
     SytrdProb p[MAX_BATCH];

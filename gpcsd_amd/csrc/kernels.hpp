@@ -430,7 +430,7 @@ void k_psd_fold_fill(gpcsd_ctx *c, const double *K, int n, long sK, int nrep, co
                      bool tab_shifts_nonneg = false);   // ... all of which are >= 0 (the arenas then count as PSD: EigArenaView::psd)
 // The temporal chain's input in ONE launch: the symmetric / antisymmetric fold of Kt = sum_c sigma2_c k_c(t_i - t_j) for
 // `nrep` hyper-parameter sets, evaluated entry by entry from the time grid (the same expressions, in the same order, as
-// k_temporal_gram followed by the eigensolver's fold), divided by a power of two >= 2 sum_c sigma2_c (>= every entry of
+// k_temporal_gram followed by the eigensolver's fold: tests/test_fold_kernels.py holds the two to the same bits), divided by a power of two >= 2 sum_c sigma2_c (>= every entry of
 // either block) and written where the tridiagonalisation reads it (eigh_arena_view of the two half-size classes), reflector
 // storage zeroed, *amax set.  Replaces temporal Gram -> fold -> absmax -> scale/copy/zero (five dependent launches).
 // Non-finite entries are zeroed and reported in status[r * status_stride] (4), as the scaling pass does.

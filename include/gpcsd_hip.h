@@ -265,6 +265,51 @@ typedef struct gpcsd_debug_grad_args {
     long nout[4];
 } gpcsd_debug_grad_args;
 int gpcsd_debug_grad_op(gpcsd_ctx *ctx, gpcsd_debug_grad_args *args);
+/* Diagnostics for the folded-basis and relayout kernels (csrc/gram.hip, csrc/eigh.hip; no reference counterpart): ONE of the k_*
+ * launchers on the context's main stream, host arrays in and out, nothing else between the caller and the kernels.  An orbit table
+ * comes from the caller as an involution perm[k] of nperm[k] points (perm[perm[i]] == i; the identity is accepted: no pair, every
+ * point its own orbit) and is built by the routine the grids' own symmetries go through: pairs in the order of their first
+ * members, then the fixed points (ns orbits, na pairs).  in[k] / out[k] are host arrays with their lengths in doubles in nin[k] /
+ * nout[k]; the furthest element the launcher can address is compared with every length before anything is uploaded.  Every output
+ * starts on the device as the bit pattern `fill` and comes back whole: what no kernel wrote still holds it (an output may be longer
+ * than its launcher's reach, at least one double).  list != 0: ops 1 and 5 also write the per-component list.
+ *   op  launcher                 perm[]            n[]                l[]                 in[]                 out[]
+ *   0   k_swap_last2             -                 n0, n1, n2         -                   in (n0 n1 n2)        out (n0 n2 n1)
+ *   1   k_swap_last2_sum         -                 n0, n1, n2, C      list_stride         in (n0 n1 C n2)      sum (n0 n2 n1), list
+ *   2   k_sym_fold_rect          rows, columns     -                  ldk                 K (rows ldk apart)   ss (ns_r ns_c), aa (na_r na_c)
+ *   3   k_sym_unfold_mat         matrix            -                  s_in                Gf (B sets s_in apart: ss, aa)   out (B n n)
+ *   4   k_fold_lfp               electrodes, time  R                  -                   Y (nx R nt)          out (nx R nt)
+ *   5   k_unfold_swap_sum        sites, time       R, C, nsP, naP     list_stride, ldin   in (nz R rows)       sum (nz nt R), list
+ *   6   k_temporal_fold_fill     time grid         -                  -                   t (nt)               A0s (B ns ns), A0a (B na na), V, tau, amax
+ *       (table: _tab)
+ *   7   k_psd_fold_fill          grid              -                  sK                  K (B or 1 of n n)    the same
+ * Op 5: nsP, naP, ldin = 0 are the launcher's defaults (unpadded blocks).  Ops 6 and 7 write where the tridiagonalisation reads
+ * (the class arenas of the temporal / spatial chain) and return, per set: both scaled blocks; V = the (ns + 64) ns words of the
+ * symmetric class's reflector storage and the word behind them, then the same for the antisymmetric class; tau = ns + 66 words and
+ * the word behind them, then na + 67; amax = the two scale words; status[set] (ints).  Op 6 takes B sets from hp: 1 or 2 by value,
+ * any number with table != 0, and honours gpcsd_set_gram_precision.  Op 7 adds s[set] to the diagonals (1 or 2 sets; sK = 0: one
+ * source) or, with table != 0, hp[set].jitter.  Both need a pair (na >= 1).  They drop whatever an earlier call left for reuse in
+ * those arenas (decomposition cache, positive-semi-definite marks): a model call afterwards decomposes again and returns the bits
+ * it returned before.
+ * rc -3: an unknown op, a null or short operand, a permutation that is no involution, a non-positive size, a stride or padded
+ * width below its minimum, a table or sets where an op has none; nothing has been launched then. */
+typedef struct gpcsd_debug_fold_args {
+    int op, B, table, list;
+    int n[4];
+    long l[4];
+    double s[4];
+    double fill;
+    const gpcsd_hparams *hp;             /* B sets (op 6; op 7 with a table) */
+    const int *perm[2];
+    int nperm[2];
+    const double *in[2];
+    long nin[2];
+    double *out[5];
+    long nout[5];
+    int *status;                         /* ops 6 and 7: at least B words */
+    int nstatus;
+} gpcsd_debug_fold_args;
+int gpcsd_debug_fold_op(gpcsd_ctx *ctx, gpcsd_debug_fold_args *args);
 /* comp_eig_D(Ks, Kt, sig2n)            utility_functions.py:44-64 ; Dvec has nx*nt entries */
 int gpcsd_eig_D(gpcsd_ctx *ctx, const double *Ks, int nx, const double *Kt, int nt,
                 const double *sig2n, int n_sig, double *Qs, double *Qt, double *Dvec);

@@ -651,7 +651,8 @@ def test_folded_gemm_1d_odd_sizes_vs_oracle(ncomp, R):
     """GPCSD1D with an odd number of electrodes and time points (fixed points of both reflections, ns != na), folded path
     against the oracle: loglik, predictions at the electrodes and at a symmetric subset of sites.  One and two temporal
     components go through the fused last product (unfold in its epilogue; partial tiles in every dimension: 36 / 35 time
-    orbits, 41 / 40 site orbits, 3 or 21 trials), three through the GEMM + relayout pair with padded column blocks."""
+    orbits, 41 / 40 site orbits, 3 or 21 trials), three through the GEMM + relayout pair with padded column blocks.  The fold,
+    unfold and relayout kernels themselves are checked tightly, entry by entry against long double, in tests/test_fold_kernels.py."""
     from gpcsd_amd.gpcsd1d import GPCSD1D
     from gpcsd_amd.covariances import GPCSDTemporalCovSE, GPCSDTemporalCovMatern
     rs = np.random.RandomState(5)
