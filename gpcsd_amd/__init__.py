@@ -7,7 +7,7 @@ fallback -- compute calls raise if the library or a GPU is missing.  Nothing tou
 """
 from . import _hip  # noqa: F401
 from . import priors, forward_models, utility_functions, covariances, predict_csd  # noqa: F401
-from . import gpcsd1d, gpcsd2d, dist  # noqa: F401
+from . import gpcsd1d, gpcsd2d, dist, kcsd  # noqa: F401
 from .gpcsd1d import GPCSD1D  # noqa: F401
 from .gpcsd2d import GPCSD2D  # noqa: F401
 from ._hip import GPCSDCapacityError, HipUnavailable  # noqa: F401

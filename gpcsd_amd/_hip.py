@@ -223,6 +223,11 @@ SIGNATURES = {
     "gpcsd_trsm_lower_trans": (_I, [_P, _DP, _I, _DP, _I, _DP]),
     "gpcsd_torus_graph": (_I, [_P, _DP, _DP, _I, _I, _DP, _I, _DP, ctypes.POINTER(_I), _DP, _DP, _DP]),
     "gpcsd_torus_graph_resident": (_I, [_P, ctypes.POINTER(_I), _I, _I, _I, _I, _I, _DP, _I, _DP, ctypes.POINTER(_I), _DP]),
+    "gpcsd_kcsd_basis_1d": (_I, [_P, _DP, _I, _DP, _I, _D, _D, _D, _DP, _DP, _I, _I, _DP]),
+    "gpcsd_kcsd_cv": (_I, [_P, _DP, _DP, _DP, _I, _I, _I, _DP, _I, _DP, _IP]),
+    "gpcsd_kcsd_cross_validate": (_I, [_P, _DP, _I, _DP, _I, _DP, _I, _DP, _I, _D, _D, _DP, _DP, _I, _DP, _I, _DP, _I, _DP, _IP, _IP,
+                                       _DP, _DP, _DP, _DP]),
+    "gpcsd_kcsd_estimate": (_I, [_P, _DP, _I, _DP, _I, _DP, _I, _DP, _I, _D, _D, _DP, _DP, _I, _D, _D, _DP, _DP, _DP, _DP]),
     "gpcsd_fetch": (_I, [_P, ctypes.c_char_p, _DP, _L]),
     "gpcsd_device_buffer": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
     "gpcsd_sample_prior": (_I, [_P, ctypes.POINTER(HParams), _I, _DP, _I, _DP]),
@@ -1449,6 +1454,63 @@ class Context:
         self._check(self._lib.gpcsd_torus_graph_resident(self._h, sites.ctypes.data_as(ctypes.POINTER(_I)), d, int(j), nz, nsel, R, _ptr(w),
                                                          B, _ptr(phi), status.ctypes.data_as(ctypes.POINTER(_I)), _ptr(chi2)))
         return self._tg_result(phi, status, chi2)
+
+    # ---- kernel CSD, 1D, Gaussian sources (kcsd.hip) ----
+    def kcsd_basis_1d(self, src, pts, R, h, sigma, gl_x, gl_w, which):
+        """(M, npts) potential (which = 0) or source (which = 1) basis of kernel CSD (gpcsd_kcsd_basis_1d)"""
+        src, pts, gl_x, gl_w = (_arr(v).reshape(-1) for v in (src, pts, gl_x, gl_w))
+        out = np.empty((src.size, pts.size))
+        self._check(self._lib.gpcsd_kcsd_basis_1d(self._h, _ptr(src), src.size, _ptr(pts), pts.size, float(R), float(h), float(sigma),
+                                                  _ptr(gl_x), _ptr(gl_w), gl_x.size, int(which), _ptr(out)))
+        return out
+
+    def kcsd_cv(self, U, s, W, lambdas):
+        """Leave-one-electrode-out table from eigen-decompositions (gpcsd_kcsd_cv): U (nR, n, n), s (nR, n), W = U^T V (nR, n, T),
+        lambdas (nlam) -> (err (nR, nlam), status (nR, nlam))"""
+        U, s, W, lambdas = _arr(U), _arr(s), _arr(W), _arr(lambdas).reshape(-1)
+        if U.ndim != 3 or U.shape[1] != U.shape[2] or s.shape != U.shape[:2] or W.ndim != 3 or W.shape[:2] != U.shape[:2]:
+            raise ValueError("kcsd_cv: U (nR, n, n), s (nR, n), W (nR, n, T)")
+        nR, n, T = W.shape
+        err = np.empty((nR, lambdas.size))
+        status = np.zeros((nR, lambdas.size), dtype=np.int32)
+        self._check(self._lib.gpcsd_kcsd_cv(self._h, _ptr(U), _ptr(s), _ptr(W), n, T, nR, _ptr(lambdas), lambdas.size, _ptr(err),
+                                            status.ctypes.data_as(_IP)))
+        return err, status
+
+    @staticmethod
+    def _kcsd_outputs(n, n_est, T, want):
+        shapes = {"csd": (n_est, T), "pot": (n, T), "k_pot": (n, n), "k_cross": (n_est, n)}
+        return {k: (np.empty(shapes[k]) if k in want else None) for k in shapes}
+
+    def kcsd_cross_validate(self, ele, V, src, est, h, sigma, gl_x, gl_w, Rs, lambdas, want=("csd", "pot", "k_pot", "k_cross")):
+        """The resident cross-validation chain (gpcsd_kcsd_cross_validate): (err, status, (R index, lambda index), outputs of the
+        selected pair by name).  Every pair singular: the table comes back with best = None."""
+        ele, src, est, gl_x, gl_w, Rs, lambdas = (_arr(v).reshape(-1) for v in (ele, src, est, gl_x, gl_w, Rs, lambdas))
+        V = _arr(V, (ele.size, np.shape(V)[-1]), "V")
+        n, T = V.shape
+        err = np.empty((Rs.size, lambdas.size))
+        status = np.zeros((Rs.size, lambdas.size), dtype=np.int32)
+        best = np.full(2, -1, dtype=np.int32)
+        out = self._kcsd_outputs(n, est.size, T, want)
+        rc = self._lib.gpcsd_kcsd_cross_validate(self._h, _ptr(ele), n, _ptr(V), T, _ptr(src), src.size, _ptr(est), est.size, float(h),
+                                                 float(sigma), _ptr(gl_x), _ptr(gl_w), gl_x.size, _ptr(Rs), Rs.size, _ptr(lambdas),
+                                                 lambdas.size, _ptr(err), status.ctypes.data_as(_IP), best.ctypes.data_as(_IP),
+                                                 _ptr(out["csd"]), _ptr(out["pot"]), _ptr(out["k_pot"]), _ptr(out["k_cross"]))
+        if rc == 1 and best[0] < 0 and status.all():
+            return err, status, None, out
+        self._check(rc)
+        return err, status, (int(best[0]), int(best[1])), out
+
+    def kcsd_estimate(self, ele, V, src, est, h, sigma, gl_x, gl_w, R, lambd, want=("csd",)):
+        """Estimates for one pair (R, lambda) (gpcsd_kcsd_estimate): outputs by name"""
+        ele, src, est, gl_x, gl_w = (_arr(v).reshape(-1) for v in (ele, src, est, gl_x, gl_w))
+        V = _arr(V, (ele.size, np.shape(V)[-1]), "V")
+        n, T = V.shape
+        out = self._kcsd_outputs(n, est.size, T, want)
+        self._check(self._lib.gpcsd_kcsd_estimate(self._h, _ptr(ele), n, _ptr(V), T, _ptr(src), src.size, _ptr(est), est.size, float(h),
+                                                  float(sigma), _ptr(gl_x), _ptr(gl_w), gl_x.size, float(R), float(lambd), _ptr(out["csd"]),
+                                                  _ptr(out["pot"]), _ptr(out["k_pot"]), _ptr(out["k_cross"])))
+        return out
 
     def fetch(self, name, shape):
         out = pinned_pool.empty(shape)

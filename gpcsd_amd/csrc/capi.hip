@@ -1435,6 +1435,7 @@ extern "C" int gpcsd_set_time(gpcsd_ctx *c, const double *t, int nt) {
 #include "capi_spectrum.inl"
 #include "capi_shift.inl"
 #include "capi_torus.inl"
+#include "capi_kcsd.inl"
 #include "capi_grad.inl"
 #include "capi_debug_grad.inl"
 #include "capi_debug_fold.inl"

@@ -214,6 +214,21 @@ void k_tg_residuals(gpcsd_ctx *c, const TgDesc &t, const double *phi, double *g,
 // chi2[p] = phi_p^T Sigma_pp^-1 phi_p with Sigma_pp = 1/W^2 sum_n w_n z_n z_n^T over rows 2p, 2p + 1 of Z (m x N)
 void k_tg_chi2(gpcsd_ctx *c, const double *Z, const double *w, const double *phi, int P, int N, double W, double *chi2, hipStream_t s);
 
+// ---------------------------------------------------------------- kernel CSD, 1D, Gaussian sources (kcsd.hip)
+constexpr int KCSD_WRES_MAX_N = 256;       // electrodes up to which a workgroup of kcsd_cv_kernel keeps its 64 columns of W in LDS
+// out (M, npts): which == 0 the potential basis b_j(pts[p]) (two-panel Gauss-Legendre, nodes gx / weights gw on [-1, 1], summed in
+// node order), which == 1 the source basis g(pts[p] - src[j]); sigma_b = R / 3
+void k_kcsd_basis(gpcsd_ctx *c, const double *src, int M, const double *pts, int npts, double R, double h, double varsigma,
+                  const double *gx, const double *gw, int ngl, int which, double *out, hipStream_t s);
+// err[r][l] = sum_i sqrt(sum_t (beta_it / a_ii)^2) with beta = U_r diag(1 / (s_r + lam_l)) W_r, a_ii = sum_k U_ik^2 / (s_k + lam_l);
+// U (nR, n, n) eigenvectors in columns, s (nR, n), W (nR, n, T), lam (nlam): device arrays.  status[r][l] = 1 and err = +inf for a
+// numerically singular pair.  beta is never stored; fixed summation order.
+void k_kcsd_cv(gpcsd_ctx *c, const double *U, const double *s, const double *W, int n, int T, int nR, const double *lam, int nlam,
+               double *err, int *status, hipStream_t st);
+// d[k] = 1 / (max(s_k, 0) + lam), sd[k] = max(s_k, 0) d[k]; *status = 1 (and zeros) for a numerically singular pair
+void k_kcsd_scale(gpcsd_ctx *c, const double *s, int n, double lam, double *d, double *sd, int *status, hipStream_t st);
+void k_kcsd_rowscale(gpcsd_ctx *c, const double *W, const double *d, int n, int T, double *out, hipStream_t st);      // out[k][t] = d[k] W[k][t]
+
 // ---------------------------------------------------------------- missing samples (masked.hip)
 // The grouped, K-scaled symmetric product G = (A^-1)_MM of m missing samples sorted by time, then electrode, cut into strips of up
 // to MASKED_STRIP samples of one time group; a tile is MASKED_TILE_STRIPS x MASKED_TILE_STRIPS strips.  One launch covers the tile

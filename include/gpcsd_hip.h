@@ -606,6 +606,50 @@ int gpcsd_torus_graph(gpcsd_ctx *ctx, const double *u_re, const double *u_im, in
  * are out of scope: fetch the phasors and use gpcsd_torus_graph); rc -3 also for j or a site out of range. */
 int gpcsd_torus_graph_resident(gpcsd_ctx *ctx, const int *sites, int d, int j, int nz, int nsel, int R, const double *weights, int B,
                                double *phi, int *status, double *chi2);
+/* Kernel CSD in one dimension with Gaussian sources.  No reference counterpart in the package; usage note: these four
+ * calls replace the KCSD1D class of the external kcsd package that the reference's comparisons construct, cross-validate and evaluate
+ * (simulation_studies/sim_from_gp_1D.py:14,112-127, simple_template_1D.py:99-105, sim_from_gp_1D_mismatch.py,
+ * auditory_lfp/fit_mean_function.py:31,112-115).  This is the project's closed-form statement of the method, not that package's
+ * table-interpolated one.
+ *
+ * One basis: out (M, npts) row-major.  which == 1, the source basis (the b_src_matrix of sim_from_gp_1D.py:114's constructor):
+ *   out[j][p] = g(pts[p] - src[j]),  g(u) = exp(-u^2 / (2 sb^2)) / (sqrt(2 pi) sb),  sb = R / 3  (not truncated at |u| = R).
+ * which == 0, the potential basis (its b_pot_matrix):
+ *   out[j][p] = 1 / (2 varsigma) int_{-R}^{R} [sqrt((u - d)^2 + h^2) - |u - d|] g(u) du,   d = pts[p] - src[j],
+ * by Gauss-Legendre with the caller's ngl nodes gl_x / weights gl_w on [-1, 1] (as gpcsd_kphi_1d) on each of the two panels
+ * [-R, c], [c, R], c = clip(d, -R, R) -- the integrand has a kink at u = d; the bracket is evaluated as h^2 / (sqrt(v^2 + h^2) + v),
+ * v = |u - d|; the 2 ngl terms are added in node order.  Accurate to ~1e-13 of the largest entry for h / R >= 0.05 at ngl = 48; the
+ * rule degrades below that.  rc -3: NULL or empty operands, non-finite input, R <= 0, h <= 0, varsigma <= 0, M < 1, ngl < 2, which
+ * not 0 / 1; GPCSD_ERR_CAPACITY: M npts >= 2^31. */
+int gpcsd_kcsd_basis_1d(gpcsd_ctx *ctx, const double *src, int M, const double *pts, int npts, double R, double h, double varsigma,
+                        const double *gl_x, const double *gl_w, int ngl, int which, double *out);
+/* The leave-one-electrode-out table of the scan in sim_from_gp_1D.py:115 (cross_validate: one refit per held-out electrode, basis
+ * width and ridge) from eigen-decompositions K_r = U_r diag(s_r) U_r^T, in closed form: with d_k = 1 / (max(s_k, 0) + lambda),
+ * beta = U diag(d) W, W = U^T V, a_i = sum_k U_ik^2 d_k = ((K + lambda I)^-1)_ii, the residual of electrode i predicted without it is
+ * beta_i / a_i, and err[r][l] = sum_i || beta_i / a_i ||_2.  U (nR, n, n) eigenvectors in columns, s (nR, n), W (nR, n, T), lambdas
+ * (nlam); err and status (nR, nlam).  A pair with s_min + lambda < n 2^-52 s_max (or not positive) is numerically singular: err =
+ * +inf, status = 1, and the other pairs keep their bits.  beta is formed tile by tile on the matrix cores and never stored; fixed
+ * summation order, no atomics: the same call returns the same bits, and an entry does not depend on which other lambda values the call
+ * holds.  rc -3: NULL or empty operands, non-finite input, lambda < 0; GPCSD_ERR_CAPACITY (before anything is read): n >
+ * GPCSD_MAX_EIG_N, nR nlam > 65535, T >= GPCSD_MAX_GEMM_LD_KMAJOR. */
+int gpcsd_kcsd_cv(gpcsd_ctx *ctx, const double *U, const double *s, const double *W, int n, int T, int nR, const double *lambdas, int nlam,
+                  double *err, int *status);
+/* The whole of sim_from_gp_1D.py:114-118 on the device: bases for every R, K = B_pot^T B_pot / M and K~ = B_src^T B_pot / M, one batched
+ * eigen-decomposition (negative eigenvalues set to 0), W = U^T V, the table of the kernel-CSD cross-validation, its argmin (best[0] = R
+ * index, best[1] = lambda index; on ties the smallest R index, then the smallest lambda index; singular pairs are never selected) and,
+ * where an output is not NULL, for the selected pair: csd (n_est, T) = K~ (K + lambda I)^-1 V, pot (n, T) = K (K + lambda I)^-1 V,
+ * k_pot (n, n) = K, k_cross (n_est, n) = K~.  ele (n), V (n, T), src (M), est (n_est), Rs (nR), lambdas (nlam).  Only V, the table and
+ * the requested outputs cross the bus.  rc 1: every pair is singular (err and status are written), or an eigen-decomposition failed;
+ * rc -3 and GPCSD_ERR_CAPACITY as the two calls above (also M, n_est >= 2^22). */
+int gpcsd_kcsd_cross_validate(gpcsd_ctx *ctx, const double *ele, int n, const double *V, int T, const double *src, int M, const double *est,
+                              int n_est, double h, double varsigma, const double *gl_x, const double *gl_w, int ngl, const double *Rs,
+                              int nR, const double *lambdas, int nlam, double *err, int *status, int *best, double *csd, double *pot,
+                              double *k_pot, double *k_cross);
+/* The estimate of sim_from_gp_1D.py:122-124 (a KCSD1D with given R_init and lambd, then values()) for one pair (R, lambda): the same
+ * chain without the table.  rc 1: K + lambda I is numerically singular. */
+int gpcsd_kcsd_estimate(gpcsd_ctx *ctx, const double *ele, int n, const double *V, int T, const double *src, int M, const double *est,
+                        int n_est, double h, double varsigma, const double *gl_x, const double *gl_w, int ngl, double R, double lambda,
+                        double *csd, double *pot, double *k_pot, double *k_cross);
 /* copy `count` doubles of the named ctx-owned device buffer to host; rc -2 if the name is unknown; rc > 0 if the
  * asynchronous gpcsd_predict_resident that produced the buffer failed numerically */
 int gpcsd_fetch(gpcsd_ctx *ctx, const char *name, double *host, long count);
