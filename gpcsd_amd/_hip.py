@@ -208,6 +208,9 @@ SIGNATURES = {
     "gpcsd_fun_gram_chunk": (_I, [_I]),
     "gpcsd_loo": (_I, [_P, ctypes.POINTER(HParams), _DP, _DP, _DP, _DP]),
     "gpcsd_loo_resident": (_I, [_P, ctypes.POINTER(HParams), _I]),
+    "gpcsd_cv_electrodes": (_I, [_P, ctypes.POINTER(HParams), _IP, _IP, _I, _DP, _DP, _DP, _DP, _IP]),
+    "gpcsd_cv_electrodes_resident": (_I, [_P, ctypes.POINTER(HParams), _IP, _IP, _I, _I]),
+    "gpcsd_efold_contract": (_I, [_P, _DP, _DP, _DP, _I, _I, _I, _I, _IP, _IP, _I, _DP, _DP, _DP, _DP, _IP]),
     "gpcsd_fisher": (_I, [_P, ctypes.POINTER(HParams), _DP, _I]),
     "gpcsd_trial_scores": (_I, [_P, ctypes.POINTER(HParams), _DP, _I]),
     "gpcsd_trial_scores_resident": (_I, [_P, ctypes.POINTER(HParams), _I]),
@@ -1190,6 +1193,54 @@ class Context:
     def loo_resident(self, hp, want_mean=True):
         """The same into the device buffers "loo_var", "loo_lpd", "loo_sse" (and "loo_mean") only; read back with fetch()."""
         self._check(self._lib.gpcsd_loo_resident(self._h, ctypes.byref(hp), int(bool(want_mean))))
+
+    # ---- leave-electrodes-out cross-validation (efold.hip, capi_cv.inl) ----
+    @staticmethod
+    def _fold_csr(folds):
+        """(fold_ptr (nfolds + 1), fold_idx) int32 arrays of a sequence of index sequences."""
+        ptr = np.zeros(len(folds) + 1, dtype=np.int32)
+        ptr[1:] = np.cumsum([len(f) for f in folds])
+        idx = np.ascontiguousarray(np.concatenate([np.asarray(f, dtype=np.int32).ravel() for f in folds]) if len(folds) else
+                                   np.zeros(0, dtype=np.int32))
+        return ptr, idx
+
+    def cv_electrodes(self, hp, shape, fold_ptr, fold_idx, want_mean=True):
+        """Leave-electrodes-out scores (gpcsd_cv_electrodes) as host arrays; shape = (nx, nt, ntrials) of the resident data, the folds
+        in CSR form (int32: fold i = fold_idx[fold_ptr[i]:fold_ptr[i + 1]]).  Dict with "var" (nx, nt), "lpd" (nfolds, ntrials),
+        "sse" (nx, ntrials), "status" (nfolds) and "mean" (nx, nt, ntrials) or None."""
+        nx, nt, R = (int(v) for v in shape)
+        ptr, idx = np.ascontiguousarray(fold_ptr, dtype=np.int32), np.ascontiguousarray(fold_idx, dtype=np.int32)
+        nf = ptr.size - 1
+        res = {"var": np.empty((nx, nt)), "lpd": np.empty((nf, R)), "sse": np.empty((nx, R)), "status": np.empty(nf, dtype=np.int32),
+               "mean": pinned_pool.empty((nx, nt, R)) if want_mean else None}
+        self._check(self._lib.gpcsd_cv_electrodes(self._h, ctypes.byref(hp), ptr.ctypes.data_as(_IP), idx.ctypes.data_as(_IP), nf,
+                                                  _ptr(res["var"]), _ptr(res["mean"]), _ptr(res["lpd"]), _ptr(res["sse"]),
+                                                  res["status"].ctypes.data_as(_IP)))
+        return res
+
+    def cv_electrodes_resident(self, hp, fold_ptr, fold_idx, want_mean=True):
+        """The same into the device buffers "cv_var", "cv_lpd", "cv_sse", "cv_status" (and "cv_mean") only; read back with fetch()."""
+        ptr, idx = np.ascontiguousarray(fold_ptr, dtype=np.int32), np.ascontiguousarray(fold_idx, dtype=np.int32)
+        self._check(self._lib.gpcsd_cv_electrodes_resident(self._h, ctypes.byref(hp), ptr.ctypes.data_as(_IP), idx.ctypes.data_as(_IP),
+                                                           ptr.size - 1, int(bool(want_mean))))
+
+    def efold_contract(self, A, W, V, folds, want_E=True):
+        """The kernels of cv_electrodes() alone (gpcsd_efold_contract): A (nx, K), W (K, nt) > 0, V (nx, R, nt), folds a sequence of
+        index sequences -> (E (nx, R, nt) or None, pdiag (nx, nt), lpd (nfolds, R), sse (nx, R), status (nfolds))."""
+        A, W, V = _arr(A), _arr(W), _arr(V)
+        nx, K = A.shape
+        nt = W.shape[1]
+        if W.shape[0] != K or V.ndim != 3 or V.shape[0] != nx or V.shape[2] != nt:
+            raise ValueError("efold_contract: A (nx, K), W (K, nt), V (nx, R, nt)")
+        R = V.shape[1]
+        ptr, idx = self._fold_csr(folds)
+        nf = len(folds)
+        E = np.empty((nx, R, nt)) if want_E else None
+        pdiag, lpd, sse, status = np.empty((nx, nt)), np.empty((nf, R)), np.empty((nx, R)), np.empty(nf, dtype=np.int32)
+        self._check(self._lib.gpcsd_efold_contract(self._h, _ptr(A), _ptr(W), _ptr(V), nx, K, nt, R, ptr.ctypes.data_as(_IP),
+                                                   idx.ctypes.data_as(_IP), nf, _ptr(E), _ptr(pdiag), _ptr(lpd), _ptr(sse),
+                                                   status.ctypes.data_as(_IP)))
+        return E, pdiag, lpd, sse, status
 
     # ---- hyper-parameter uncertainty (fisher.hip, capi_fisher.inl) ----
     def fisher(self, hp, ng):

@@ -1427,6 +1427,7 @@ extern "C" int gpcsd_set_time(gpcsd_ctx *c, const double *t, int nt) {
 #include "capi_operators.inl"
 #include "capi_fused.inl"
 #include "capi_posterior.inl"
+#include "capi_cv.inl"
 #include "capi_sample.inl"
 #include "capi_features.inl"
 #include "capi_functionals.inl"

@@ -250,32 +250,58 @@ extern "C" int gpcsd_predict_var(gpcsd_ctx *c, const gpcsd_hparams *hp, const do
 //   c[x][t] = sum_{x',i'} Qs[x][x']^2 Qt[t][i']^2 / D[x'][i']          two squared-operand products, every term >= 0
 //   beta_r  = Qs ((Qs^T Y_r Qt) / D) Qt^T                               the prediction front's Bm, V = Qs Bm, then gemm_loo
 // in the merged (unfolded, eigenvector) basis, which is correct for every model the library accepts.  Outputs: loo_var (nx, nt),
-// loo_lpd / loo_sse (nx, R), loo_mean (nx, nt, R) when asked.  (A front of its own: the jitter of loglik, no sites and no times.)
+// loo_lpd / loo_sse (nx, R), loo_mean (nx, nt, R) when asked.  (A front of its own, shared with gpcsd_cv_electrodes: the jitter of loglik, no sites, no times.)
 // ------------------------------------------------------------------------------------------------------------------
-static int loo_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, bool want_mean) {
+// The request check and the front that gpcsd_loo and gpcsd_cv_electrodes (capi_cv.inl) share: the decomposition with loglik's jitter
+// and V = Qs ((Qs^T Y_r Qt) / D) = K^-1 y_r in the temporal eigen-basis, (nx, R, nt) in "loo_V".  The launches behind the joined
+// decomposition are all on the main stream, so their order among themselves is free (loo's bits do not depend on it).
+static void loo_request(const gpcsd_ctx *c, const gpcsd_hparams *hp, const char *who) {
     GP_REQUIRE(hp != nullptr, -3, "null hparams");
     GP_REQUIRE(c->d_lfp != nullptr, -4, "lfp not set (call gpcsd_set_lfp)");
-    const int nx = c->nx, nt = c->nt, R = c->ntrials;
-    const long RT = (long)R * nt, nrow = (long)nx * R;
+    const long RT = (long)c->ntrials * c->nt, nrow = (long)c->nx * c->ntrials;
     // (checked before anything is read: one row of the projected data is a flat GEMM operand row)
     GP_REQUIRE(RT < GPCSD_MAX_GEMM_LD_KMAJOR && nrow < (1L << 31), GPCSD_ERR_CAPACITY,
-               "loo: ntrials * nt = %ld (or nx * ntrials = %ld) exceeds the capacity of one operand row (%ld doubles; "
-               "GPCSD_MAX_GEMM_LD_KMAJOR)", RT, nrow, (long)GPCSD_MAX_GEMM_LD_KMAJOR);
+               "%s: ntrials * nt = %ld (or nx * ntrials = %ld) exceeds the capacity of one operand row (%ld doubles; "
+               "GPCSD_MAX_GEMM_LD_KMAJOR)", who, RT, nrow, (long)GPCSD_MAX_GEMM_LD_KMAJOR);
+}
+struct LooFront {
+    EigState e;
+    double *V = nullptr;
+};
+static int loo_front(gpcsd_ctx *c, const gpcsd_hparams *hp, LooFront &f) {
+    const int nx = c->nx, nt = c->nt, R = c->ntrials;
+    const long RT = (long)R * nt;
     // the scratch of the prediction calls is rewritten below: whatever an earlier queued prediction still owes is collected first
     if (int rc = drain_async(c)) return rc;
-    EigState e = front_half(c, hp, hp->jitter);    // the jitter of loglik (gpcsd1d.py:117)
-    hipStream_t s = c->stream;
+    f.e = front_half(c, hp, hp->jitter);           // the jitter of loglik (gpcsd1d.py:117)
     double *W = c->buf<double>("proj_W", (size_t)nx * RT);
     double *Bm = c->buf<double>("pred_B", (size_t)nx * RT);
-    double *V = c->buf<double>("loo_V", (size_t)nx * RT);
+    f.V = c->buf<double>("loo_V", (size_t)nx * RT);
+    pred_data_spatial(c, f.e, W, c->d_lfp, R);
+    join_temporal(c, f.e, nullptr, false);         // nobody reads sum(log D) here
+    pred_data_temporal(c, f.e, W, Bm, R);
+    GemmDesc g3;                          // V[x][(r,i')] = sum_x' Qs[x][x'] Bm[x'][(r,i')]
+    g3.M = nx; g3.N = (int)RT; g3.K = nx;
+    g3.A = f.e.Qs; g3.lda = nx; g3.B = Bm; g3.ldb = RT; g3.C = f.V; g3.ldc = RT;
+    g3.prof_name = "gemm_loo_V";
+    gemm_f64(c, g3, c->stream);
+    return 0;
+}
+
+static int loo_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, bool want_mean) {
+    loo_request(c, hp, "loo");
+    const int nx = c->nx, nt = c->nt, R = c->ntrials;
+    const long RT = (long)R * nt, nrow = (long)nx * R;
+    LooFront f;
+    if (int rc = loo_front(c, hp, f)) return rc;
+    EigState &e = f.e;
+    hipStream_t s = c->stream;
     double *H = c->buf<double>("loo_H", (size_t)nx * nt);
     double *QtT = c->buf<double>("loo_QtT", (size_t)nt * nt);
     double *cdiag = c->buf<double>("loo_c", (size_t)nx * nt);
     double *var = c->buf<double>("loo_var", (size_t)nx * nt);
     double *lpd = c->buf<double>("loo_lpd", (size_t)nrow), *sse = c->buf<double>("loo_sse", (size_t)nrow);
     double *mean = want_mean ? c->buf<double>("loo_mean", (size_t)nx * RT) : nullptr;
-    pred_data_spatial(c, e, W, c->d_lfp, R);
-    join_temporal(c, e, nullptr, false);           // nobody reads sum(log D) here
     VarDesc v1;                           // H[x][i'] = sum_x' Qs[x][x']^2 Dinv[x'][i']
     v1.A = e.Qs; v1.lda = nx; v1.B = e.Dinv; v1.ldb = nt;
     v1.nrow = nx; v1.ncol = nt; v1.K = nx; v1.sq_a = true; v1.list = H;
@@ -288,14 +314,8 @@ static int loo_impl(gpcsd_ctx *c, const gpcsd_hparams *hp, bool want_mean) {
     v2.prof_name = "gemm_var_c";
     gemm_var(c, v2, s);
     k_loo_var(c, cdiag, var, (long)nx * nt, s);
-    pred_data_temporal(c, e, W, Bm, R);
-    GemmDesc g3;                          // V[x][(r,i')] = sum_x' Qs[x][x'] Bm[x'][(r,i')]
-    g3.M = nx; g3.N = (int)RT; g3.K = nx;
-    g3.A = e.Qs; g3.lda = nx; g3.B = Bm; g3.ldb = RT; g3.C = V; g3.ldc = RT;
-    g3.prof_name = "gemm_loo_V";
-    gemm_f64(c, g3, s);
     LooDesc l;                            // beta[(x,r)][t] = sum_i' V[(x,r)][i'] Qt[t][i'], and everything behind it
-    l.V = V; l.ldv = nt; l.Qt = e.Qt; l.ldq = nt; l.c = cdiag; l.y = c->d_lfp;
+    l.V = f.V; l.ldv = nt; l.Qt = e.Qt; l.ldq = nt; l.c = cdiag; l.y = c->d_lfp;
     l.K = nt; l.nt = nt; l.R = R; l.nrow = nrow;
     l.mean = mean; l.lpd = lpd; l.sse = sse;
     gemm_loo(c, l, s);

@@ -1018,6 +1018,7 @@ void gemm_pred_at(gpcsd_ctx *c, const PredAtDesc &d, hipStream_t s) {
 // The two products of a posterior variance (gpcsd_predict_var), VarDesc in kernels.hpp:
 //
 //   SQA:   G[z][i']       = sum_x' M1[z][x']^2 Dinv[x'][i']
+//   PAIR:  G[p][i']       = sum_x' M1[pa[p]][x'] M1[pb[p]][x'] Dinv[x'][i']                     (SQA is pa[p] = pb[p] = p: the same bits)
 //   else:  out[c][z][j]   = prior[z] kd[c]       - sum_i' G[z][i'] P_c[i'][j]^2                 plane c < C
 //          out[C][z][j]   = prior[z] sum_c kd[c] - sum_i' G[z][i'] (sum_c P_c[i'][j])^2         plane C
 //
@@ -1039,10 +1040,14 @@ struct VarK {
     double *list;                // [plane < C][nrow][ncol]
     double *sum;                 // plane C
     int tiles_n;
+    const int *pa, *pb;          // VAR_PAIR: the two rows of A whose product is row p of the operand ([nrow] each)
 };
 
-template <bool SQA>
+enum { VAR_PLAIN = 0, VAR_SQA = 1, VAR_PAIR = 2 };
+
+template <int AMODE>
 __global__ __launch_bounds__(256) void gemm_var_kernel(VarK g) {
+    constexpr bool SQA = AMODE == VAR_SQA, PAIR = AMODE == VAR_PAIR;
     constexpr int NT = 256, BK = 16, BM = 64, BN = 64;
     using TileA = Tile<BM, false, NT, BK>;    // G / M1: global [rows][K]
     using TileB = Tile<BN, true, NT, BK>;     // Pcat / Dinv: global [K][cols]
@@ -1074,16 +1079,31 @@ __global__ __launch_bounds__(256) void gemm_var_kernel(VarK g) {
 
     const int K = g.K;
     unsigned offA[TileA::PER_THREAD], offB[TileB::PER_THREAD];
-    TileA::setup(offA, g.lda, m0, g.nrow, tid);
+    unsigned offA2[PAIR ? TileA::PER_THREAD : 1];
+    int rowa[PAIR ? TileA::PER_THREAD : 1], rowb[PAIR ? TileA::PER_THREAD : 1];
+    if constexpr (PAIR) {                                      // gathered rows: offsets from A itself (the host checks they fit 32 bits)
+#pragma unroll
+        for (int i = 0; i < TileA::PER_THREAD; ++i) {
+            const int go = m0 + oa0 + TileA::DO * i, p = go < g.nrow ? go : g.nrow - 1;
+            rowa[i] = g.pa[p];
+            rowb[i] = g.pb[p];
+            offA[i] = (unsigned)(((long)rowa[i] * g.lda + ka0) * 8);
+            offA2[i] = (unsigned)(((long)rowb[i] * g.lda + ka0) * 8);
+        }
+    } else {
+        TileA::setup(offA, g.lda, m0, g.nrow, tid);
+    }
     TileB::setup(offB, g.ldb, n0, g.ncol, tid);
-    const double *const baseA = TileA::tile_base(g.A, g.lda, m0);
+    const double *const baseA = TileA::tile_base(g.A, g.lda, PAIR ? 0 : m0);
     const double *const baseB = TileB::tile_base(g.B + (all ? 0L : (long)plane * g.ncol), g.ldb, n0);       // wave-uniform
     const int cstep = g.ncol * 8;                              // bytes from one component's column to the next one's
     const int nk = (K + BK - 1) / BK, nfull = K / BK;
     double ra[TileA::PER_THREAD], rb[TileB::PER_THREAD];
+    double ra2[PAIR ? TileA::PER_THREAD : 1];
 
     auto load_full = [&](int t) {
         TileA::gload(ra, TileA::rsrc(baseA, g.lda, t), 0, offA);
+        if constexpr (PAIR) TileA::gload(ra2, TileA::rsrc(baseA, g.lda, t), 0, offA2);
         const __amdgpu_buffer_rsrc_t rsb = TileB::rsrc(baseB, g.ldb, t);
         TileB::gload(rb, rsb, 0, offB);
         for (int cc = 1; cc < ncomp; ++cc) {                   // (wave-uniform: the sum plane only)
@@ -1098,7 +1118,17 @@ __global__ __launch_bounds__(256) void gemm_var_kernel(VarK g) {
             load_full(t);
         } else {                                               // partial K tile: out-of-range k reads the last valid one
             const int kleft = K - t * BK;
-            TileA::gload_tail(ra, TileA::rsrc(baseA, g.lda, t), 0, g.lda, m0, g.nrow, kleft, tid);
+            if constexpr (PAIR) {
+                const __amdgpu_buffer_rsrc_t rsa = TileA::rsrc(baseA, g.lda, t);
+                const int kc = ka0 < kleft ? ka0 : kleft - 1;
+#pragma unroll
+                for (int i = 0; i < TileA::PER_THREAD; ++i) {
+                    ra[i] = TileA::bload(rsa, (unsigned)(((long)rowa[i] * g.lda + kc) * 8), 0);
+                    ra2[i] = TileA::bload(rsa, (unsigned)(((long)rowb[i] * g.lda + kc) * 8), 0);
+                }
+            } else {
+                TileA::gload_tail(ra, TileA::rsrc(baseA, g.lda, t), 0, g.lda, m0, g.nrow, kleft, tid);
+            }
             const __amdgpu_buffer_rsrc_t rsb = TileB::rsrc(baseB, g.ldb, t);
             TileB::gload_tail(rb, rsb, 0, g.ldb, n0, g.ncol, kleft, tid);
             for (int cc = 1; cc < ncomp; ++cc) {
@@ -1114,6 +1144,9 @@ __global__ __launch_bounds__(256) void gemm_var_kernel(VarK g) {
         if (SQA) {
 #pragma unroll
             for (int i = 0; i < TileA::PER_THREAD; ++i) ra[i] *= ra[i];
+        } else if constexpr (PAIR) {
+#pragma unroll
+            for (int i = 0; i < TileA::PER_THREAD; ++i) ra[i] *= ra2[i];
         } else {
 #pragma unroll
             for (int i = 0; i < TileB::PER_THREAD; ++i) rb[i] *= rb[i];
@@ -1208,7 +1241,10 @@ __global__ __launch_bounds__(256) void gemm_var_kernel(VarK g) {
 void gemm_var(gpcsd_ctx *c, const VarDesc &d, hipStream_t s) {
     GP_REQUIRE(d.nrow > 0 && d.ncol > 0 && d.K > 0 && d.C >= 1 && d.C <= GPCSD_MAX_TEMPORAL && d.A && d.B && d.list, -3,
                "gemm_var: bad problem");
-    GP_REQUIRE(!d.sq_a || (d.C == 1 && !d.sum && !d.prior), -3, "gemm_var: the squared-A form is one plain product");
+    const bool pair = d.pair_a != nullptr;
+    GP_REQUIRE(!(d.sq_a || pair) || (d.C == 1 && !d.sum && !d.prior), -3, "gemm_var: the squared-A form is one plain product");
+    GP_REQUIRE(!pair || (!d.sq_a && d.pair_b && d.a_rows > 0), -3, "gemm_var: the pair form names both rows and the rows of A");
+    GP_REQUIRE(!pair || (long)d.a_rows * d.lda < (1L << 28), GPCSD_ERR_CAPACITY, "gemm_var: A exceeds the capacity of gathered row offsets");
     // 32-bit byte offsets inside one K tile of one block tile: 64 rows of A, 16 rows of B and the C components of a slot
     GP_REQUIRE(d.lda < (1L << 22) && d.ldb < GPCSD_MAX_GEMM_LD_KMAJOR && (long)d.C * d.ncol <= d.ldb, GPCSD_ERR_CAPACITY,
                "gemm_var: leading dimension %ld exceeds the capacity of one operand row", d.lda < (1L << 22) ? d.ldb : d.lda);
@@ -1227,9 +1263,11 @@ void gemm_var(gpcsd_ctx *c, const VarDesc &d, hipStream_t s) {
     }
     k.list = d.list; k.sum = d.sum;
     k.tiles_n = ceil_div(d.ncol, 64);
+    k.pa = d.pair_a; k.pb = d.pair_b;
     const dim3 grid((unsigned)tiles, (unsigned)planes);
-    if (d.sq_a) hipLaunchKernelGGL((gemm_var_kernel<true>), grid, dim3(256), 0, s, k);
-    else hipLaunchKernelGGL((gemm_var_kernel<false>), grid, dim3(256), 0, s, k);
+    if (pair) hipLaunchKernelGGL((gemm_var_kernel<VAR_PAIR>), grid, dim3(256), 0, s, k);
+    else if (d.sq_a) hipLaunchKernelGGL((gemm_var_kernel<VAR_SQA>), grid, dim3(256), 0, s, k);
+    else hipLaunchKernelGGL((gemm_var_kernel<VAR_PLAIN>), grid, dim3(256), 0, s, k);
     GP_HIP(hipGetLastError());
 }
 

@@ -107,6 +107,7 @@ void gemm_pred_at(gpcsd_ctx *c, const PredAtDesc &d, hipStream_t s);
 //   sq_a:  out[z][i] = sum_k A[z][k]^2 B[k][i]                                  (G = (M1 o M1) Dinv; C = 1, prior = nullptr)
 //   else:  list[c][z][j] = prior[z] kd[c] - sum_k A[z][k] B[k][c * ncol + j]^2                                   c = 0..C-1
 //          sum[z][j]     = prior[z] sum_c kd[c] - sum_k A[z][k] (sum_c B[k][c * ncol + j])^2     (the components are correlated)
+//   pair:  out[p][i] = sum_k A[pair_a[p]][k] A[pair_b[p]][k] B[k][i]       (sq_a with gathered rows: the Gram blocks of gpcsd_cv_electrodes)
 // prior == nullptr: the plain product is stored (no subtraction).  One launch: grid y = the C (+ 1 when sum != nullptr) planes.
 struct VarDesc {
     const double *A = nullptr;      // [nrow][K] row-major
@@ -115,6 +116,8 @@ struct VarDesc {
     long ldb = 0;
     int nrow = 0, ncol = 0, K = 0, C = 1;
     bool sq_a = false;
+    const int *pair_a = nullptr, *pair_b = nullptr;     // device [nrow] each, entries in [0, a_rows); sq_a stays false
+    int a_rows = 0;                 // rows of A in the pair form
     const double *prior = nullptr;  // [nrow]
     double kd[GPCSD_MAX_TEMPORAL] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     double *list = nullptr;         // (C, nrow, ncol)
@@ -145,6 +148,28 @@ struct LooDesc {
 };
 void gemm_loo(gpcsd_ctx *c, const LooDesc &d, hipStream_t s);
 void k_loo_var(gpcsd_ctx *c, const double *cdiag, double *var, long n, hipStream_t s);      // var = 1 / cdiag elementwise
+
+// ---------------------------------------------------------------- leave-electrodes-out cross-validation (efold.hip)
+// Factor and solve of the blocks G_j = (K^-1)_FF of every fold F and temporal eigen-index j (gpcsd_cv_electrodes): Cholesky, log det,
+// diag(G_j^-1) and e = G_j^-1 u for every trial, with the sums over j of log det, u^T e and e^2 formed in a fixed order.  Folds in
+// CSR form; row0[fold] = first row of the fold's packed lower triangle in Gp (rows i (i + 1) / 2 + k, k <= i, in fold order),
+// mem_fold[m] = the fold of member m of fold_idx.  Outputs indexed by ELECTRODE: pdiag[a][j], sse[a][r], E[(a, r)][j] (rows of
+// electrodes in no fold are not written); lpd[fold][r]; status[fold] = 1 where some G_j lost positive definiteness (NaN outputs).
+struct EfoldDesc {
+    const double *Gp = nullptr;     // [rows][nt]
+    const double *V = nullptr;      // [(x, r)][nt]
+    const int *fold_ptr = nullptr, *fold_idx = nullptr, *row0 = nullptr, *mem_fold = nullptr;      // device
+    int nfolds = 0, nt = 0, R = 0;
+    double *E = nullptr;            // [(x, r)][nt] or nullptr
+    double *pdiag = nullptr;        // [nx][nt]
+    double *lpd = nullptr;          // [nfolds][R]
+    double *sse = nullptr;          // [nx][R]
+    int *status = nullptr;          // [nfolds]
+    double *partials = nullptr;     // efold_partials() doubles of scratch
+    double *part_ld = nullptr, *part_q = nullptr, *part_sse = nullptr;      // (set by efold_solve)
+};
+long efold_partials(const EfoldDesc &d, int nmem);
+void efold_solve(gpcsd_ctx *c, EfoldDesc d, const int *h_fold_ptr, hipStream_t s);
 
 // ---------------------------------------------------------------- band phase and phase locking (phase.hip)
 // Analytic signal of X[z][t][m] under the complex operator A = Are + i Aim (nsel, nts) -- band-pass + Hilbert along t as one matrix,

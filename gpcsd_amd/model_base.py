@@ -962,6 +962,117 @@ class GPCSDModel:
             total = float(sh.allreduce_sum(np.array([total]))[0])
         return total
 
+    CV_MAX_FOLD = 16                     # GPCSD_CV_MAX_FOLD
+
+    @classmethod
+    def _fold_arrays(cls, folds, nx):
+        """folds of cv_electrodes -> (fold_ptr (nfolds + 1), fold_idx) int32 arrays, the CSR form of the C ABI, order kept.  None: one
+        fold per electrode; an int k: electrode i in fold i % k; otherwise a sequence of index sequences.  ValueError on a malformed
+        list (no fold, an empty fold, an index outside [0, nx), an electrode held out twice), GPCSDCapacityError on a fold above
+        CV_MAX_FOLD electrodes.  Checked on whole arrays: a list of hundreds of folds costs no Python loop beyond its conversion."""
+        nx = int(nx)
+        if folds is None:
+            sizes, idx = np.ones(nx, dtype=np.int64), np.arange(nx, dtype=np.int64)
+        elif isinstance(folds, (int, np.integer)) and not isinstance(folds, bool):
+            k = int(folds)
+            if not 1 <= k <= nx:
+                raise ValueError("cv_electrodes: folds=%d, need 1 <= k <= nx = %d" % (k, nx))
+            idx = np.argsort(np.arange(nx) % k, kind="stable")                  # fold 0: 0, k, 2k, ...; fold 1: 1, k + 1, ...
+            sizes = np.bincount(np.arange(nx) % k, minlength=k)
+        else:
+            try:
+                parts = [np.atleast_1d(np.asarray(f)) for f in folds]
+            except TypeError:
+                raise ValueError("cv_electrodes: folds is None, an int or a sequence of index sequences")
+            if len(parts) == 0:
+                raise ValueError("cv_electrodes: no folds")
+            if any(f.ndim != 1 or f.size == 0 for f in parts):
+                raise ValueError("cv_electrodes: an empty fold (or one that is not a sequence of indices)")
+            sizes = np.array([f.size for f in parts], dtype=np.int64)
+            idx = np.concatenate(parts)
+            if not np.issubdtype(idx.dtype, np.integer):
+                if idx.dtype.kind not in "fiu" or not np.all(np.equal(np.mod(idx, 1), 0)):
+                    raise ValueError("cv_electrodes: folds hold non-integer indices")
+            idx = idx.astype(np.int64)
+            if idx.min() < 0 or idx.max() >= nx:
+                raise ValueError("cv_electrodes: a fold has an index outside [0, %d)" % nx)
+            if np.bincount(idx, minlength=nx).max() > 1:
+                raise ValueError("cv_electrodes: an electrode is held out twice")
+        if sizes.max() > cls.CV_MAX_FOLD:
+            raise _hip.GPCSDCapacityError("cv_electrodes: a fold of %d electrodes exceeds CV_MAX_FOLD = %d (predict_masked with a "
+                                          "dead-electrode mask holds out larger sets)" % (sizes.max(), cls.CV_MAX_FOLD))
+        ptr = np.zeros(sizes.size + 1, dtype=np.int32)
+        ptr[1:] = np.cumsum(sizes)
+        return ptr, np.ascontiguousarray(idx, dtype=np.int32)
+
+    @staticmethod
+    def _fold_tuple(ptr, idx):
+        idx, p = idx.astype(np.int64), ptr.tolist()
+        return tuple(idx[a:b] for a, b in zip(p[:-1], p[1:]))
+
+    @classmethod
+    def _normalise_folds(cls, folds, nx):
+        """... as the tuple of 1-D int arrays that becomes `cv_folds`."""
+        ptr, idx = cls._fold_arrays(folds, nx)
+        return cls._fold_tuple(ptr, idx)
+
+    def cv_electrodes(self, folds=None, mean=True, resident=False):
+        """Leave-ELECTRODES-out cross-validation of the model under its current hyper-parameters, in closed form and without a
+        refit: every sample of a fold's electrodes is held out at once and predicted from the other electrodes.  `loo()` keeps an
+        electrode's neighbours in time, which explain almost all of a temporally smooth sample; this score asks whether the SPATIAL
+        model -- the forward model, R and ell_s -- predicts a channel it has not seen, and is the score the CSD literature uses to
+        compare estimators.  Returns the total log predictive density, the sum of `cv_lpd`, as a float.
+
+        folds: None (one fold per electrode), an int k (electrode i in fold i % k) or a sequence of index sequences: disjoint, 1 to
+        16 electrodes each, indices in [0, nx); electrodes in no fold are allowed.  A malformed list raises ValueError and a larger
+        fold GPCSDCapacityError, both before the device is touched (predict_masked holds out larger sets).
+
+        K is the covariance of `loglik()` and `loo()`: (Ks + JITTER I) (x) Kt + noise through (Qs (x) Qt) diag(D) (Qs (x) Qt)^T, a
+        noise list on the eigen-index, user-defined temporal covariances allowed.  For a fold F of f electrodes (K^-1)_FF is
+        Qt blockdiag_j(G_j) Qt^T with G_j[a][b] = sum_x' Qs[a][x'] Qs[b][x'] / D[x'][j], so with u_j,r = (K^-1 y_r)[F] in the temporal
+        eigen-basis and e_j,r = G_j^-1 u_j,r (the held-out residual y - yhat in that basis) the call sets
+
+          cv_folds   tuple of int arrays      the folds as given, order kept
+          cv_lpd     (nfolds, ntrials)        1/2 sum_j log det G_j - 1/2 sum_j u^T e - 1/2 f nt log(2 pi): the JOINT log predictive
+                                              density of the block, with its 2 pi constant as in `loo`
+          cv_sse     (nx, ntrials)            sum_j e[a]^2 = sum over t of (y - yhat)^2 of electrode a (Qt is orthogonal)
+          cv_var     (nx, nt)                 sum_j Qt[t][j]^2 (G_j^-1)[a][a]: predictive variance of the NOISY held-out sample
+          cv_mean    (nx, nt, ntrials)        y - sum_j Qt[t][j] e[a], or None with mean=False (the other outputs keep their bits)
+          cv_status  (nfolds,) int            1: some G_j of the fold lost positive definiteness; its outputs are NaN and it is
+                                              left out of the returned total
+
+        Rows of electrodes in no fold are NaN.  For a one-trial model and folds=None, `np.sqrt(cv_sse[:, 0]).sum()` is kCSD's
+        cross-validation error sum_i ||V_i - Vhat_i||_2 (KCSD1D's leave-one-electrode-out scan), so GPCSD and kCSD can be ranked
+        on the same held-out-channel score.  The sums are formed in a fixed order: the same call gives the same bits, and a fold's
+        outputs depend neither on the other folds of the call nor on their order.  resident=True: zero-copy device views as in
+        `loo` (`cv_status` stays a host array).  `csd_pred`, `lfp_pred`, `t_pred`, the `loo_*` and the `*_var` attributes are left
+        alone.  Under trial sharding the per-trial arrays are this rank's block of trials, `cv_var` is the same on every rank and
+        the returned total is summed over the ranks.  No reference counterpart."""
+        ptr, idx = self._fold_arrays(folds, np.atleast_3d(self.lfp).shape[0])
+        ctx = self._sync_device()
+        hp, _keep = self._hparams(self.JITTER)             # the jitter of loglik
+        nx, nt, R_local = self._local_lfp().shape
+        nf = ptr.size - 1
+        if resident:
+            ctx.cv_electrodes_resident(hp, ptr, idx, want_mean=mean)
+            self.cv_var = ctx.device_array("cv_var", (nx, nt))
+            self.cv_lpd = ctx.device_array("cv_lpd", (nf, R_local))
+            self.cv_sse = ctx.device_array("cv_sse", (nx, R_local))
+            self.cv_mean = ctx.device_array("cv_mean", (nx, nt, R_local)) if mean else None
+            self.cv_status = np.array(ctx.fetch("cv_status", ((nf + 1) // 2,)).view(np.int32)[:nf])
+            lpd = ctx.fetch("cv_lpd", (nf, R_local))
+        else:
+            res = ctx.cv_electrodes(hp, (nx, nt, R_local), ptr, idx, want_mean=mean)
+            self.cv_var, self.cv_lpd, self.cv_sse, self.cv_mean = res["var"], res["lpd"], res["sse"], res["mean"]
+            self.cv_status = res["status"]
+            lpd = res["lpd"]
+        self.cv_folds = self._fold_tuple(ptr, idx)
+        total = float(np.sum(lpd[self.cv_status == 0]))
+        sh = getattr(self, "_sharding", None)
+        if sh is not None:
+            total = float(sh.allreduce_sum(np.array([total]))[0])
+        return total
+
     # ------------------------------------------------------------------ hyper-parameter uncertainty
     def _fisher_args(self, who):
         """(ctx, hp, keep, ng) of the score / information calls: the model of loglik(), scalar noise only."""

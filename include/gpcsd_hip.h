@@ -62,6 +62,9 @@ extern "C" {
 /*   GPCSD_MAX_REGIONS         labelled regions J of gpcsd_region_features / gpcsd_sample_features (one row of workgroups per region
  *                           in the pass that folds a region's partial results)                                                   */
 #define GPCSD_MAX_REGIONS         4096
+/*   GPCSD_CV_MAX_FOLD         electrodes in one fold of gpcsd_cv_electrodes (the f x f block of a fold is factored by one lane: 136
+ *                           doubles at the limit; gpcsd_predict_masked holds out larger sets)                                    */
+#define GPCSD_CV_MAX_FOLD         16
 #define GPCSD_ERR_CAPACITY      (-7)
 /* values per region and column of gpcsd_region_features / gpcsd_sample_features */
 #define GPCSD_NFEAT             10
@@ -466,6 +469,38 @@ int gpcsd_loo(gpcsd_ctx *ctx, const gpcsd_hparams *hp, double *var, double *mean
  * (nx*ntrials each) and, when want_mean != 0, "loo_mean" (nx*nt*ntrials) for gpcsd_fetch / gpcsd_device_buffer.  Waits for its own
  * work: a numerical failure (rc > 0) is returned by the call itself.  The buffers of the predictions are left alone. */
 int gpcsd_loo_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, int want_mean);
+/* Leave-electrodes-out cross-validation in closed form (no reference counterpart): the model of gpcsd_loo, but whole ELECTRODES are
+ * held out -- every sample of the fold's electrodes at once, so that the prediction rests on the spatial model (the forward model,
+ * R, ell_s) and not on the electrode's own neighbours in time.  Folds in CSR form: fold i holds the electrodes
+ * fold_idx[fold_ptr[i] .. fold_ptr[i + 1]), 1 to GPCSD_CV_MAX_FOLD of them, all folds disjoint, indices in [0, nx); electrodes in
+ * no fold are allowed.  For a fold F of f electrodes (K^-1)_FF = Qt blockdiag_j(G_j) Qt^T with one f x f matrix per temporal
+ * eigen-index j,
+ *   G_j[a][b] = sum_x' Qs[a][x'] Qs[b][x'] / D[x'][j],   u_j,r = (Qs ((Qs^T Y_r Qt) / D))[F][j],   e_j,r = G_j^-1 u_j,r
+ * (e: the held-out residual y - yhat in the temporal eigen-basis), and
+ *   lpd[F][r]    = 1/2 sum_j log det G_j - 1/2 sum_j u_j,r^T e_j,r - 1/2 f nt log(2 pi)   joint log predictive density of the block
+ *   sse[a][r]    = sum_j e_j,r[a]^2           = sum_t (y - yhat)^2 of electrode a (Qt is orthogonal)
+ *   var[a][t]    = sum_j Qt[t][j]^2 (G_j^-1)[a][a]              predictive variance of the NOISY held-out sample
+ *   mean[a][t][r] = y - sum_j Qt[t][j] e_j,r[a]
+ * Outputs (any may be NULL; mean == NULL also skips its stores and its product on the device, with the same bits for the rest):
+ * var (nx, nt); mean (nx, nt, ntrials); lpd (nfolds, ntrials); sse (nx, ntrials); status (nfolds) ints, 1 = some G_j of the fold
+ * lost positive definiteness (its outputs are NaN).  Rows of electrodes in no fold are NaN.  All sums are formed in a fixed order
+ * without atomics: the same call returns the same bits, and a fold's outputs depend neither on the other folds of the call nor on
+ * their order.  rc -3: null hp / fold arrays, nfolds <= 0, an empty fold, an index out of range, a repeated electrode; rc -4: no
+ * resident trials; GPCSD_ERR_CAPACITY: a fold above GPCSD_CV_MAX_FOLD, or the row capacities of gpcsd_loo -- all returned before
+ * anything is read or launched, and the context stays usable. */
+int gpcsd_cv_electrodes(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const int *fold_ptr, const int *fold_idx, int nfolds, double *var,
+                        double *mean, double *lpd, double *sse, int *status);
+/* Same computation (no reference counterpart), results left in the named device buffers "cv_var" (nx*nt), "cv_lpd" (nfolds*ntrials),
+ * "cv_sse" (nx*ntrials), "cv_status" (nfolds ints) and, when want_mean != 0, "cv_mean" (nx*nt*ntrials). */
+int gpcsd_cv_electrodes_resident(gpcsd_ctx *ctx, const gpcsd_hparams *hp, const int *fold_ptr, const int *fold_idx, int nfolds,
+                                 int want_mean);
+/* The kernels of gpcsd_cv_electrodes alone, on host arrays (no reference counterpart; upload, the Gram product, factor and solve,
+ * the ordered sums, download): A (nx, K), W (K, nt) > 0 and V (nx, R, nt) give G_j[a][b] = sum_k A[a][k] A[b][k] W[k][j] per fold
+ * and e = G_j^-1 V[F][r][j]; outputs E (nx, R, nt) (may be NULL), pdiag (nx, nt) with pdiag[a][j] = (G_j^-1)[a][a], lpd (nfolds, R),
+ * sse (nx, R), status (nfolds).  Rows of electrodes in no fold are NaN.  Return codes as gpcsd_cv_electrodes (no -4). */
+int gpcsd_efold_contract(gpcsd_ctx *ctx, const double *A, const double *W, const double *V, int nx, int K, int nt, int R,
+                         const int *fold_ptr, const int *fold_idx, int nfolds, double *E, double *pdiag, double *lpd, double *sse,
+                         int *status);
 /* Hyper-parameter uncertainty.  NO REFERENCE COUNTERPART: fit() (gpcsd1d.py:193-220, gpcsd2d.py:232-259) returns a point estimate
  * and stops; tr(K^-1 d_i K K^-1 d_j K) on the (nx nt)^2 covariance is out of its reach.  Extends gpcsd_loglik_grad: the same model
  * (Ks + hp->jitter I, a user-defined temporal Gram with its derivative matrices from gpcsd_set_host_temporal_dgram allowed), the
