@@ -1,5 +1,8 @@
 """ctypes binding of libgpcsd_hip.so (include/gpcsd_hip.h).  No CPU fallback: if the HIP library is missing
-or no GPU is visible, every compute entry point raises."""
+or no GPU is visible, every compute entry point raises.  A posterior call is one method with `resident=False` as a trailing
+keyword and the same keys either way, read from its `*_outputs` table; predict_resident, the queued call, is the exception
+("Host and resident forms")."""
+import collections
 import ctypes
 import os
 import threading
@@ -427,15 +430,93 @@ def _sites_times(z, tstar):
     return _arr(z), _arr(tstar).reshape(-1)
 
 
-def _sum_list_outputs(type_code, shape, C, want_lists=True):
-    """Pinned host outputs of the form "csd / lfp x sum / list": "csd", "lfp" of `shape` and "csd_list", "lfp_list" with a leading
-    axis of the C temporal components; None for a quantity type_code does not ask for (and for the lists unless want_lists)."""
-    bufs = {}
-    for name, bit in (("csd", PRED_CSD), ("lfp", PRED_LFP)):
-        on = bool(type_code & bit)
-        bufs[name] = pinned_pool.empty(tuple(shape)) if on else None
-        bufs[name + "_list"] = pinned_pool.empty((C,) + tuple(shape)) if on and want_lists else None
-    return bufs
+# ---- what each posterior call produces.  One table per call, read by its host form (host_outputs) and by its resident form
+# (device_views) alike; the names of the result buffers are written here and nowhere else in the package.
+Output = collections.namedtuple("Output", "key buffer shape pinned")      # shape None: the request does not produce this output
+
+
+def _quantities(type_code):
+    return [(name, bool(type_code & bit)) for name, bit in (("csd", PRED_CSD), ("lfp", PRED_LFP))]
+
+
+def _sum_list_table(prefix, type_code, shape, C, want_lists=True):
+    """The form "csd / lfp x list / sum": "csd_list", "lfp_list" with a leading axis of the C temporal components and "csd", "lfp" of
+    `shape`, in the buffers prefix + key, page-locked on the host; absent for a quantity type_code does not ask for (and the
+    lists unless want_lists).  Every table lists its outputs in the order its C call takes them."""
+    return tuple(Output(name + suf, prefix + name + suf, lead + tuple(shape) if on and (want_lists or not suf) else None, True)
+                 for name, on in _quantities(type_code) for suf, lead in (("_list", (C,)), ("", ())))
+
+
+def predict_outputs(type_code, shape, C, want_lists=True):
+    """predict, predict_at, predict_masked and the queued calls; shape = (nz, ntstar, ntrials)."""
+    return _sum_list_table("pred_out_", type_code, shape, C, want_lists)
+
+
+def predict_var_outputs(type_code, shape, C):
+    """shape = (nz, ntstar)."""
+    return _sum_list_table("pred_var_", type_code, shape, C)
+
+
+def predict_functionals_outputs(type_code, J, R, C):
+    """Per quantity q "q_mean" (J, R), "q_cov" and "q_prior" (J, J), each behind its "_list" form."""
+    return tuple(Output("%s_%s%s" % (name, kind, suf), "fun_%s_%s%s" % (kind, name, suf), lead + shape if on else None, False)
+                 for name, on in _quantities(type_code) for kind, shape in (("mean", (J, R)), ("cov", (J, J)), ("prior", (J, J)))
+                 for suf, lead in (("_list", (C,)), ("", ())))
+
+
+def _held_out_table(prefix, shape, nrows, want_mean):
+    nx, nt, R = shape
+    return (Output("var", prefix + "var", (nx, nt), False), Output("mean", prefix + "mean", (nx, nt, R) if want_mean else None, True),
+            Output("lpd", prefix + "lpd", (nrows, R), False), Output("sse", prefix + "sse", (nx, R), False))
+
+
+def loo_outputs(shape, want_mean=True):
+    """shape = (nx, nt, ntrials) of the resident data; "lpd" has a row per electrode."""
+    return _held_out_table("loo_", shape, shape[0], want_mean)
+
+
+def cv_electrodes_outputs(shape, nfolds, want_mean=True):
+    """As loo_outputs with a row of "lpd" per fold.  ("status" is int32 and not in the table: Context.cv_electrodes.)"""
+    return _held_out_table("cv_", shape, nfolds, want_mean)
+
+
+def trial_scores_outputs(R, ng):
+    return (Output("scores", "trial_scores", (R, ng), False),)
+
+
+def sample_posterior_outputs(type_code, shape, keep=True):
+    """shape = (nz, ntstar, ntrials, nsamples)."""
+    return tuple(Output(name, "post_sample_" + name, tuple(shape) if on and keep else None, True) for name, on in _quantities(type_code))
+
+
+def sample_features_outputs(type_code, shape, J, keep_draws=False):
+    """The raw slots "feat_csd" / "feat_lfp" (J, NFEAT, ntrials, nsamples), then the draws of sample_posterior_outputs if kept."""
+    feats = tuple(Output("feat_" + name, "feat_" + name, (J, NFEAT) + tuple(shape[2:]) if on else None, True)
+                  for name, on in _quantities(type_code))
+    return feats + sample_posterior_outputs(type_code, shape, keep_draws)
+
+
+def _flag_table(outputs, mask, shape, pinned=True):
+    """A table from the (key, buffer) pairs of a signal-analysis call: pair i of `shape` if bit i of mask is set."""
+    return tuple(Output(k, buf, tuple(int(v) for v in shape) if mask & (1 << i) else None, pinned) for i, (k, buf) in enumerate(outputs))
+
+
+def host_outputs(table):
+    """Host arrays to receive the outputs of a table: key -> array, None for an output the request does not produce."""
+    return {o.key: None if o.shape is None else pinned_pool.empty(o.shape) if o.pinned else np.empty(o.shape) for o in table}
+
+
+def device_views(ctx, table):
+    """The outputs of a table where a resident call left them: key -> zero-copy DeviceArray (ctx.device_array), None as above."""
+    return {o.key: None if o.shape is None else ctx.device_array(o.buffer, o.shape) for o in table}
+
+
+def _present(res):
+    return {k: v for k, v in res.items() if v is not None}
+
+
+def _ptrs(bufs):
+    return [_ptr(v) for v in bufs.values()]
 
 
 class DeviceArray:
@@ -1098,12 +1179,11 @@ class Context:
         """shape = (nz, ntstar, ntrials).  Returns dict of arrays for the requested type.  at=True: gpcsd_predict_at (any ntstar,
         the training axis of the cross Grams contracted) instead of gpcsd_predict."""
         z, tstar = _sites_times(z, tstar)
-        nz, ntstar, R = shape
-        bufs = _sum_list_outputs(type_code, (nz, ntstar, R), hp.n_temporal, want_lists)
+        bufs = host_outputs(predict_outputs(type_code, shape, hp.n_temporal, want_lists))
         fn = self._lib.gpcsd_predict_at if at else self._lib.gpcsd_predict
-        self._check(fn(self._h, ctypes.byref(hp), _ptr(z), nz, _ptr(tstar), tstar.size, int(type_code),
-                       _ptr(bufs["csd_list"]), _ptr(bufs["csd"]), _ptr(bufs["lfp_list"]), _ptr(bufs["lfp"])))
-        return {k: v for k, v in bufs.items() if v is not None}
+        self._check(fn(self._h, ctypes.byref(hp), _ptr(z), shape[0], _ptr(tstar), tstar.size, int(type_code),
+                       *_ptrs(bufs)))
+        return _present(bufs)
 
     def predict_resident(self, hp, z, tstar, type_code, want_lists=True, at=False):
         """Compute the posterior mean into device buffers only (no PCIe traffic); read back with fetch().  at=True:
@@ -1112,21 +1192,28 @@ class Context:
         fn = self._lib.gpcsd_predict_at_resident if at else self._lib.gpcsd_predict_resident
         self._check(fn(self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size, int(type_code), int(bool(want_lists))))
 
-    def predict_var(self, hp, z, tstar, type_code):
-        """Posterior variances (gpcsd_predict_var) as host arrays: dict with "csd" / "lfp" (nz, ntstar) and "csd_list" / "lfp_list"
-        (C, nz, ntstar) for the requested type."""
-        z, tstar = _sites_times(z, tstar)
-        nz = z.shape[0]
-        bufs = _sum_list_outputs(type_code, (nz, tstar.size), hp.n_temporal)
-        self._check(self._lib.gpcsd_predict_var(self._h, ctypes.byref(hp), _ptr(z), nz, _ptr(tstar), tstar.size, int(type_code),
-                                                _ptr(bufs["csd_list"]), _ptr(bufs["csd"]), _ptr(bufs["lfp_list"]), _ptr(bufs["lfp"])))
-        return {k: v for k, v in bufs.items() if v is not None}
+    def _either_form(self, name, table, resident, args, flags=()):
+        """Posterior call `name` on one request: gpcsd_<name>_resident(ctx, *args, *flags) and the views of its table, or
+        gpcsd_<name>(ctx, *args, a host pointer per output of the table) and the host arrays.  key -> result, None where absent."""
+        if resident:
+            self._check(getattr(self._lib, "gpcsd_%s_resident" % name)(self._h, *args, *flags))
+            return device_views(self, table)
+        bufs = host_outputs(table)
+        self._check(getattr(self._lib, "gpcsd_" + name)(self._h, *args, *_ptrs(bufs)))
+        return bufs
 
-    def predict_var_resident(self, hp, z, tstar, type_code):
-        """The same into the device buffers "pred_var_csd", "pred_var_lfp" and their "_list" forms only; read back with fetch()."""
+    def predict_views(self, type_code, shape, C, want_lists=True):
+        """What the last predict_resident, queued pair or resident masked call of this request left, under the keys of predict(), as
+        zero-copy views.  device_array drains the context's streams: this is the step predict_resident leaves to its caller."""
+        return _present(device_views(self, predict_outputs(type_code, shape, C, want_lists)))
+
+    def predict_var(self, hp, z, tstar, type_code, resident=False):
+        """Posterior variances (gpcsd_predict_var): dict with "csd" / "lfp" (nz, ntstar) and "csd_list" / "lfp_list" (C, nz, ntstar)
+        for the requested type -- host arrays, or with resident=True (gpcsd_predict_var_resident) zero-copy views."""
         z, tstar = _sites_times(z, tstar)
-        self._check(self._lib.gpcsd_predict_var_resident(self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size,
-                                                         int(type_code)))
+        table = predict_var_outputs(type_code, (z.shape[0], tstar.size), hp.n_temporal)
+        args = (ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size, int(type_code))
+        return _present(self._either_form("predict_var", table, resident, args))
 
     def var_contract(self, G, P, C, prior_s, kd):
         """out (C + 1, nz, nts): prior_s[z] kd[c] - sum_k G[z, k] P[k, c * nts + j]**2, and the component sum's plane (the sum taken
@@ -1140,30 +1227,15 @@ class Context:
         self._check(self._lib.gpcsd_var_contract(self._h, _ptr(G), nz, K, _ptr(P), int(C), nts, _ptr(prior_s), _ptr(kd), _ptr(out)))
         return out
 
-    def predict_functionals(self, hp, z, tstar, W, type_code, ntrials):
-        """Posterior of linear functionals (gpcsd_predict_functionals) as host arrays: per requested quantity q the keys "q_mean"
-        (J, ntrials), "q_cov", "q_prior" (J, J) and their "_list" forms with a leading axis of the C temporal components."""
+    def predict_functionals(self, hp, z, tstar, W, type_code, ntrials, resident=False):
+        """Posterior of linear functionals (gpcsd_predict_functionals): per requested quantity q the keys "q_mean" (J, ntrials),
+        "q_cov", "q_prior" (J, J) and their "_list" forms with a leading axis of the C temporal components -- host arrays, or with
+        resident=True (gpcsd_predict_functionals_resident) zero-copy views."""
         z, tstar = _sites_times(z, tstar)
         W = _arr(W)
-        J, C, R = W.shape[0], hp.n_temporal, int(ntrials)
-        bufs = {}
-        for name, bit in (("csd", PRED_CSD), ("lfp", PRED_LFP)):
-            on = bool(type_code & bit)
-            for kind, shape in (("mean", (J, R)), ("cov", (J, J)), ("prior", (J, J))):
-                bufs["%s_%s_list" % (name, kind)] = np.empty((C,) + shape) if on else None
-                bufs["%s_%s" % (name, kind)] = np.empty(shape) if on else None
-        order = ["%s_%s%s" % (name, kind, suf) for name in ("csd", "lfp") for kind in ("mean", "cov", "prior") for suf in ("_list", "")]
-        self._check(self._lib.gpcsd_predict_functionals(self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size, _ptr(W), J,
-                                                        int(type_code), *[_ptr(bufs[k]) for k in order]))
-        return {k: v for k, v in bufs.items() if v is not None}
-
-    def predict_functionals_resident(self, hp, z, tstar, W, type_code):
-        """The same into the device buffers "fun_mean_csd", "fun_cov_csd", "fun_prior_csd", their "_list" forms and the "lfp" ones
-        only; read back with fetch()."""
-        z, tstar = _sites_times(z, tstar)
-        W = _arr(W)
-        self._check(self._lib.gpcsd_predict_functionals_resident(self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size,
-                                                                 _ptr(W), W.shape[0], int(type_code)))
+        table = predict_functionals_outputs(type_code, W.shape[0], int(ntrials), hp.n_temporal)
+        args = (ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size, _ptr(W), W.shape[0], int(type_code))
+        return _present(self._either_form("predict_functionals", table, resident, args))
 
     def fun_gram(self, A, s=None, B=None):
         """out (C + 1, J, N): out[p, j, k] = sum_{b, i} A[p, b, j, i] s[b, i] B[b, k, i], plane C with sum_p A[p] in A's place.
@@ -1181,18 +1253,12 @@ class Context:
         self._check(self._lib.gpcsd_fun_gram(self._h, _ptr(A), C, nb, J, K, _ptr(s), _ptr(B), N, _ptr(out)))
         return out
 
-    def loo(self, hp, shape, want_mean=True):
-        """Leave-one-out scores (gpcsd_loo) as host arrays; shape = (nx, nt, ntrials) of the resident data.  Dict with "var" (nx, nt),
-        "lpd" and "sse" (nx, ntrials) and "mean" (nx, nt, ntrials) or None."""
-        nx, nt, R = (int(v) for v in shape)
-        res = {"var": np.empty((nx, nt)), "lpd": np.empty((nx, R)), "sse": np.empty((nx, R)),
-               "mean": pinned_pool.empty((nx, nt, R)) if want_mean else None}
-        self._check(self._lib.gpcsd_loo(self._h, ctypes.byref(hp), _ptr(res["var"]), _ptr(res["mean"]), _ptr(res["lpd"]), _ptr(res["sse"])))
-        return res
-
-    def loo_resident(self, hp, want_mean=True):
-        """The same into the device buffers "loo_var", "loo_lpd", "loo_sse" (and "loo_mean") only; read back with fetch()."""
-        self._check(self._lib.gpcsd_loo_resident(self._h, ctypes.byref(hp), int(bool(want_mean))))
+    def loo(self, hp, shape, want_mean=True, resident=False):
+        """Leave-one-out scores (gpcsd_loo); shape = (nx, nt, ntrials) of the resident data.  Dict with "var" (nx, nt), "lpd" and
+        "sse" (nx, ntrials) and "mean" (nx, nt, ntrials) or None -- host arrays, or with resident=True (gpcsd_loo_resident)
+        zero-copy views."""
+        table = loo_outputs(tuple(int(v) for v in shape), want_mean)
+        return self._either_form("loo", table, resident, (ctypes.byref(hp),), (int(bool(want_mean)),))
 
     # ---- leave-electrodes-out cross-validation (efold.hip, capi_cv.inl) ----
     @staticmethod
@@ -1204,25 +1270,25 @@ class Context:
                                    np.zeros(0, dtype=np.int32))
         return ptr, idx
 
-    def cv_electrodes(self, hp, shape, fold_ptr, fold_idx, want_mean=True):
-        """Leave-electrodes-out scores (gpcsd_cv_electrodes) as host arrays; shape = (nx, nt, ntrials) of the resident data, the folds
-        in CSR form (int32: fold i = fold_idx[fold_ptr[i]:fold_ptr[i + 1]]).  Dict with "var" (nx, nt), "lpd" (nfolds, ntrials),
-        "sse" (nx, ntrials), "status" (nfolds) and "mean" (nx, nt, ntrials) or None."""
-        nx, nt, R = (int(v) for v in shape)
+    def cv_electrodes(self, hp, shape, fold_ptr, fold_idx, want_mean=True, resident=False):
+        """Leave-electrodes-out scores (gpcsd_cv_electrodes); shape = (nx, nt, ntrials) of the resident data, the folds in CSR form
+        (int32: fold i = fold_idx[fold_ptr[i]:fold_ptr[i + 1]]).  Dict with "var" (nx, nt), "lpd" (nfolds, ntrials), "sse"
+        (nx, ntrials) and "mean" (nx, nt, ntrials) or None -- host arrays, or with resident=True (gpcsd_cv_electrodes_resident)
+        zero-copy views -- and "status" (nfolds), a host int32 array either way."""
         ptr, idx = np.ascontiguousarray(fold_ptr, dtype=np.int32), np.ascontiguousarray(fold_idx, dtype=np.int32)
         nf = ptr.size - 1
-        res = {"var": np.empty((nx, nt)), "lpd": np.empty((nf, R)), "sse": np.empty((nx, R)), "status": np.empty(nf, dtype=np.int32),
-               "mean": pinned_pool.empty((nx, nt, R)) if want_mean else None}
-        self._check(self._lib.gpcsd_cv_electrodes(self._h, ctypes.byref(hp), ptr.ctypes.data_as(_IP), idx.ctypes.data_as(_IP), nf,
-                                                  _ptr(res["var"]), _ptr(res["mean"]), _ptr(res["lpd"]), _ptr(res["sse"]),
-                                                  res["status"].ctypes.data_as(_IP)))
-        return res
-
-    def cv_electrodes_resident(self, hp, fold_ptr, fold_idx, want_mean=True):
-        """The same into the device buffers "cv_var", "cv_lpd", "cv_sse", "cv_status" (and "cv_mean") only; read back with fetch()."""
-        ptr, idx = np.ascontiguousarray(fold_ptr, dtype=np.int32), np.ascontiguousarray(fold_idx, dtype=np.int32)
-        self._check(self._lib.gpcsd_cv_electrodes_resident(self._h, ctypes.byref(hp), ptr.ctypes.data_as(_IP), idx.ctypes.data_as(_IP),
-                                                           ptr.size - 1, int(bool(want_mean))))
+        table = cv_electrodes_outputs(tuple(int(v) for v in shape), nf, want_mean)
+        args = (self._h, ctypes.byref(hp), ptr.ctypes.data_as(_IP), idx.ctypes.data_as(_IP), nf)
+        if resident:
+            self._check(self._lib.gpcsd_cv_electrodes_resident(*args, int(bool(want_mean))))
+            res = device_views(self, table)
+            # "cv_status" holds nfolds int32 in an even count of them: read back as doubles
+            res["status"] = np.array(self.fetch("cv_status", ((nf + 1) // 2,)).view(np.int32)[:nf])
+            return res
+        res = host_outputs(table)
+        status = np.empty(nf, dtype=np.int32)
+        self._check(self._lib.gpcsd_cv_electrodes(*args, *_ptrs(res), status.ctypes.data_as(_IP)))
+        return dict(res, status=status)
 
     def efold_contract(self, A, W, V, folds, want_E=True):
         """The kernels of cv_electrodes() alone (gpcsd_efold_contract): A (nx, K), W (K, nt) > 0, V (nx, R, nt), folds a sequence of
@@ -1249,15 +1315,16 @@ class Context:
         self._check(self._lib.gpcsd_fisher(self._h, ctypes.byref(hp), _ptr(info), int(ng)))
         return info
 
-    def trial_scores(self, hp, ntrials, ng):
-        """Per-trial scores d log p(y_r) / d theta_i of the resident trials (gpcsd_trial_scores): (ntrials, ng)."""
-        scores = np.empty((int(ntrials), int(ng)))
+    def trial_scores(self, hp, ntrials, ng, resident=False):
+        """Per-trial scores d log p(y_r) / d theta_i of the resident trials (gpcsd_trial_scores): (ntrials, ng) -- a host array, or
+        with resident=True (gpcsd_trial_scores_resident) a zero-copy view."""
+        table = trial_scores_outputs(int(ntrials), int(ng))
+        if resident:
+            self._check(self._lib.gpcsd_trial_scores_resident(self._h, ctypes.byref(hp), int(ng)))
+            return device_views(self, table)["scores"]
+        scores = host_outputs(table)["scores"]
         self._check(self._lib.gpcsd_trial_scores(self._h, ctypes.byref(hp), _ptr(scores), int(ng)))
         return scores
-
-    def trial_scores_resident(self, hp, ng):
-        """The same into the device buffer "trial_scores" only; read back with fetch()."""
-        self._check(self._lib.gpcsd_trial_scores_resident(self._h, ctypes.byref(hp), int(ng)))
 
     def loo_contract(self, V, Qt, c, Y, R, want_mean=True):
         """The last product of loo() alone (gpcsd_loo_contract): V (nx * R, K), Qt (nt, K), c (nx, nt), Y (nx * R, nt) ->
@@ -1283,23 +1350,14 @@ class Context:
         m8 = np.ascontiguousarray(mask != 0, dtype=np.uint8)
         return m8, m8.shape[2]
 
-    def predict_masked(self, hp, mask, z, tstar, type_code, shape, want_lists=True):
-        """gpcsd_predict_masked: as predict(at=True) on the observed samples only.  shape = (nz, ntstar, ntrials)."""
+    def predict_masked(self, hp, mask, z, tstar, type_code, shape, want_lists=True, resident=False):
+        """gpcsd_predict_masked: as predict(at=True) on the observed samples only.  shape = (nz, ntstar, ntrials).  resident=True
+        (gpcsd_predict_masked_resident): zero-copy views of the buffers of predict_resident instead of host arrays."""
         z, tstar = _sites_times(z, tstar)
         m8, mt = self._mask_bytes(mask)
-        nz, ntstar, R = shape
-        bufs = _sum_list_outputs(type_code, (nz, ntstar, R), hp.n_temporal, want_lists)
-        self._check(self._lib.gpcsd_predict_masked(self._h, ctypes.byref(hp), m8.ctypes.data_as(_P), mt, _ptr(z), nz, _ptr(tstar),
-                                                   tstar.size, int(type_code), _ptr(bufs["csd_list"]), _ptr(bufs["csd"]),
-                                                   _ptr(bufs["lfp_list"]), _ptr(bufs["lfp"])))
-        return {k: v for k, v in bufs.items() if v is not None}
-
-    def predict_masked_resident(self, hp, mask, z, tstar, type_code, want_lists=True):
-        """The same into the device buffers of predict_resident only; read back with fetch()."""
-        z, tstar = _sites_times(z, tstar)
-        m8, mt = self._mask_bytes(mask)
-        self._check(self._lib.gpcsd_predict_masked_resident(self._h, ctypes.byref(hp), m8.ctypes.data_as(_P), mt, _ptr(z), z.shape[0],
-                                                            _ptr(tstar), tstar.size, int(type_code), int(bool(want_lists))))
+        table = predict_outputs(type_code, shape, hp.n_temporal, want_lists)
+        args = (ctypes.byref(hp), m8.ctypes.data_as(_P), mt, _ptr(z), shape[0], _ptr(tstar), tstar.size, int(type_code))
+        return _present(self._either_form("predict_masked", table, resident, args, (int(bool(want_lists)),)))
 
     def loglik_masked(self, hp, mask, ntrials):
         """gpcsd_loglik_masked: ((sum log det A_OO, sum of the quadratic forms), per-trial rows (ntrials, 2), n_obs)."""
@@ -1352,11 +1410,9 @@ class Context:
             raise ValueError("analytic: x must be (nz, nts, M)")
         nz, nts, M = x.shape
         Are, Aim = self._operator_parts(A, nts)
-        mask = self._analytic_mask(want)
-        out = {k: pinned_pool.empty((nz, Are.shape[0], M)) if mask & (1 << i) else None for i, (k, _) in enumerate(self.ANALYTIC_OUTPUTS)}
-        self._check(self._lib.gpcsd_analytic(self._h, _ptr(x), nz, nts, M, _ptr(Are), _ptr(Aim), Are.shape[0], _ptr(out["phase"]),
-                                             _ptr(out["amp"]), _ptr(out["u_re"]), _ptr(out["u_im"])))
-        return {k: v for k, v in out.items() if v is not None}
+        out = host_outputs(_flag_table(self.ANALYTIC_OUTPUTS, self._analytic_mask(want), (nz, Are.shape[0], M)))
+        self._check(self._lib.gpcsd_analytic(self._h, _ptr(x), nz, nts, M, _ptr(Are), _ptr(Aim), Are.shape[0], *_ptrs(out)))
+        return _present(out)
 
     def analytic_resident(self, src_name, src_offset, shape, A, want=("phase",)):
         """The same on the named device buffer `src_name` from `src_offset` doubles on, read as shape = (nz, nts, M)
@@ -1368,7 +1424,13 @@ class Context:
         self._check(self._lib.gpcsd_analytic_resident(self._h, src_name.encode(), int(src_offset), nz, nts, M, _ptr(Are), _ptr(Aim),
                                                       Are.shape[0], mask))
         self.phasor_generation += 1          # (model_base.plv forms a type's phasors again if another call has replaced them)
-        return {k: self.device_array(buf, (nz, Are.shape[0], M)) for i, (k, buf) in enumerate(self.ANALYTIC_OUTPUTS) if mask & (1 << i)}
+        return _present(device_views(self, _flag_table(self.ANALYTIC_OUTPUTS, mask, (nz, Are.shape[0], M))))
+
+    def phasors(self, shape):
+        """(u_re, u_im): zero-copy views (nz, nsel, M) of the unit phasors the last analytic_resident left."""
+        return tuple(device_views(self, _flag_table(self.ANALYTIC_OUTPUTS[2:], 3, shape)).values())
+
+    PLV_OUTPUTS = (("c_re", "plv_re"), ("c_im", "plv_im"), ("plv", "plv_abs"))
 
     def plv(self, u_re, u_im, want_c=True):
         """PLV of all site pairs from host unit phasors (nz, nsel, R, S) (gpcsd_plv): (c_re, c_im, plv), each (S, nsel, nz, nz);
@@ -1377,16 +1439,15 @@ class Context:
         if u_re.ndim != 4 or u_re.shape != u_im.shape:
             raise ValueError("plv: u_re and u_im must both be (nz, nsel, R, S)")
         nz, nsel, R, S = u_re.shape
-        c_re, c_im = (np.empty((S, nsel, nz, nz)), np.empty((S, nsel, nz, nz))) if want_c else (None, None)
-        out = np.empty((S, nsel, nz, nz))
-        self._check(self._lib.gpcsd_plv(self._h, _ptr(u_re), _ptr(u_im), nz, nsel, R, S, _ptr(c_re), _ptr(c_im), _ptr(out)))
-        return c_re, c_im, out
+        out = host_outputs(_flag_table(self.PLV_OUTPUTS, 7 if want_c else 4, (S, nsel, nz, nz), pinned=False))
+        self._check(self._lib.gpcsd_plv(self._h, _ptr(u_re), _ptr(u_im), nz, nsel, R, S, *_ptrs(out)))
+        return tuple(out.values())
 
     def plv_resident(self, nz, nsel, R, S=1):
-        """The same on the phasors analytic_resident left in "phasor_re" / "phasor_im" (gpcsd_plv_resident): zero-copy views
-        (c_re, c_im, plv) of "plv_re", "plv_im", "plv_abs", each (S, nsel, nz, nz)."""
+        """The same on the phasors analytic_resident left (gpcsd_plv_resident): zero-copy views (c_re, c_im, plv), each
+        (S, nsel, nz, nz)."""
         self._check(self._lib.gpcsd_plv_resident(self._h, int(nz), int(nsel), int(R), int(S)))
-        return tuple(self.device_array(b, (int(S), int(nsel), int(nz), int(nz))) for b in ("plv_re", "plv_im", "plv_abs"))
+        return tuple(device_views(self, _flag_table(self.PLV_OUTPUTS, 7, (S, nsel, nz, nz))).values())
 
     # ---- power spectrum, cross-spectrum and coherence (spectrum.hip) ----
     SPECTRUM_OUTPUTS = (("power", "spec_power"), ("re", "spec_re"), ("im", "spec_im"))
@@ -1399,6 +1460,11 @@ class Context:
             raise ValueError("want may name %s" % (names,))
         return sum(1 << names.index(w) for w in set(want))
 
+    @classmethod
+    def _spectrum_table(cls, mask, nz, nrow, R, S):
+        """"psd" (nz, nrow, S), pageable on the host, ahead of the wanted ones of SPECTRUM_OUTPUTS (nz, nrow, R, S)."""
+        return (Output("psd", "spec_psd", (nz, nrow, S), False),) + _flag_table(cls.SPECTRUM_OUTPUTS, mask, (nz, nrow, R, S))
+
     def power_spectrum(self, x, A, want=()):
         """Trial-averaged power of the host array x (nz, nts, R, S) under the spectral operator A (nrow, nts) (gpcsd_power_spectrum):
         dict with "psd" (nz, nrow, S) and the wanted ones of "power", "re", "im", each (nz, nrow, R, S); the others are not stored."""
@@ -1407,15 +1473,10 @@ class Context:
             raise ValueError("power_spectrum: x must be (nz, nts, R, S)")
         nz, nts, R, S = x.shape
         Are, Aim = self._operator_parts(A, nts)
-        mask = self._spectrum_mask(want)
         nrow = Are.shape[0]
-        out = {k: pinned_pool.empty((nz, nrow, R, S)) if mask & (1 << i) else None for i, (k, _) in enumerate(self.SPECTRUM_OUTPUTS)}
-        psd = np.empty((nz, nrow, S))
-        self._check(self._lib.gpcsd_power_spectrum(self._h, _ptr(x), nz, nts, R, S, _ptr(Are), _ptr(Aim), nrow, _ptr(psd), _ptr(out["power"]),
-                                                   _ptr(out["re"]), _ptr(out["im"])))
-        res = {"psd": psd}
-        res.update((k, v) for k, v in out.items() if v is not None)
-        return res
+        out = host_outputs(self._spectrum_table(self._spectrum_mask(want), nz, nrow, R, S))
+        self._check(self._lib.gpcsd_power_spectrum(self._h, _ptr(x), nz, nts, R, S, _ptr(Are), _ptr(Aim), nrow, *_ptrs(out)))
+        return _present(out)
 
     def power_spectrum_resident(self, src_name, src_offset, shape, A, want=()):
         """The same on the named device buffer `src_name` from `src_offset` doubles on, read as shape = (nz, nts, R, S)
@@ -1427,9 +1488,9 @@ class Context:
         nrow = Are.shape[0]
         self._check(self._lib.gpcsd_power_spectrum_resident(self._h, src_name.encode(), int(src_offset), nz, nts, R, S, _ptr(Are), _ptr(Aim),
                                                             nrow, mask))
-        res = {"psd": self.device_array("spec_psd", (nz, nrow, S))}
-        res.update((k, self.device_array(buf, (nz, nrow, R, S))) for i, (k, buf) in enumerate(self.SPECTRUM_OUTPUTS) if mask & (1 << i))
-        return res
+        return _present(device_views(self, self._spectrum_table(mask, nz, nrow, R, S)))
+
+    XSPEC_OUTPUTS = (("s_re", "xspec_re"), ("s_im", "xspec_im"), ("coh", "xspec_coh"))
 
     def cross_spectrum(self, X_re, X_im, want_coh=True):
         """Cross-spectral matrix of all site pairs from host coefficients (nz, nrow, R, S) (gpcsd_cross_spectrum): (s_re, s_im, coh),
@@ -1438,16 +1499,15 @@ class Context:
         if X_re.ndim != 4 or X_re.shape != X_im.shape:
             raise ValueError("cross_spectrum: X_re and X_im must both be (nz, nrow, R, S)")
         nz, nrow, R, S = X_re.shape
-        s_re, s_im = np.empty((S, nrow, nz, nz)), np.empty((S, nrow, nz, nz))
-        coh = np.empty((S, nrow, nz, nz)) if want_coh else None
-        self._check(self._lib.gpcsd_cross_spectrum(self._h, _ptr(X_re), _ptr(X_im), nz, nrow, R, S, _ptr(s_re), _ptr(s_im), _ptr(coh)))
-        return s_re, s_im, coh
+        out = host_outputs(_flag_table(self.XSPEC_OUTPUTS, 7 if want_coh else 3, (S, nrow, nz, nz), pinned=False))
+        self._check(self._lib.gpcsd_cross_spectrum(self._h, _ptr(X_re), _ptr(X_im), nz, nrow, R, S, *_ptrs(out)))
+        return tuple(out.values())
 
     def cross_spectrum_resident(self, nz, nrow, R, S=1):
-        """The same on the coefficients power_spectrum_resident left in "spec_re" / "spec_im" (gpcsd_cross_spectrum_resident):
-        zero-copy views (s_re, s_im, coh) of "xspec_re", "xspec_im", "xspec_coh", each (S, nrow, nz, nz)."""
+        """The same on the coefficients power_spectrum_resident left (gpcsd_cross_spectrum_resident): zero-copy views
+        (s_re, s_im, coh), each (S, nrow, nz, nz)."""
         self._check(self._lib.gpcsd_cross_spectrum_resident(self._h, int(nz), int(nrow), int(R), int(S)))
-        return tuple(self.device_array(b, (int(S), int(nrow), int(nz), int(nz))) for b in ("xspec_re", "xspec_im", "xspec_coh"))
+        return tuple(device_views(self, _flag_table(self.XSPEC_OUTPUTS, 7, (S, nrow, nz, nz))).values())
 
     # ---- phase-difference torus graph (torus.hip) ----
     def trsm_lower_trans(self, L, B):
@@ -1597,20 +1657,14 @@ class Context:
 
     def sample_posterior(self, hp, z, tstar, type_code, nsamples, seed, R, xi=None, eps=None, resident=False):
         """Joint posterior draws (gpcsd_sample_posterior): dict with "csd" / "lfp" (nz, ntstar, R, nsamples) for the requested type
-        -- host arrays, or with resident=True nothing (the draws stay in "post_sample_csd" / "post_sample_lfp").  xi, eps: host
-        normals (R, nsamples, ns, ntt) / (R, nsamples, nx, nt), or both None for the device generator."""
+        -- host arrays, or with resident=True (gpcsd_sample_posterior_resident) zero-copy views.  xi, eps: host normals
+        (R, nsamples, ns, ntt) / (R, nsamples, nx, nt), or both None for the device generator."""
         z, tstar = _sites_times(z, tstar)
         xi = None if xi is None else _arr(xi)
         eps = None if eps is None else _arr(eps)
-        args = (self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size, int(type_code), int(nsamples), int(seed),
-                _ptr(xi), _ptr(eps))
-        if resident:
-            self._check(self._lib.gpcsd_sample_posterior_resident(*args))
-            return {}
-        bufs = {name: pinned_pool.empty((z.shape[0], tstar.size, int(R), int(nsamples))) if type_code & bit else None
-                for name, bit in (("csd", PRED_CSD), ("lfp", PRED_LFP))}
-        self._check(self._lib.gpcsd_sample_posterior(*args, _ptr(bufs["csd"]), _ptr(bufs["lfp"])))
-        return {k: v for k, v in bufs.items() if v is not None}
+        table = sample_posterior_outputs(type_code, (z.shape[0], tstar.size, int(R), int(nsamples)))
+        args = (ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size, int(type_code), int(nsamples), int(seed), _ptr(xi), _ptr(eps))
+        return _present(self._either_form("sample_posterior", table, resident, args))
 
     # ---- region features of a field and of posterior draws (features.hip) ----
     @staticmethod
@@ -1659,32 +1713,18 @@ class Context:
     def sample_features(self, hp, z, tstar, type_code, nsamples, seed, R, labels, J, band=False, floor=1e-10, keep_draws=False,
                         xi=None, eps=None, resident=False):
         """Region features of posterior draws, reduced inside the sampler (gpcsd_sample_features): dict with "feat_csd" / "feat_lfp"
-        (J, NFEAT, R * nsamples) and, with keep_draws, "csd" / "lfp" (nz, ntstar, R, nsamples) for the requested type -- host arrays,
-        or with resident=True zero-copy views of "feat_csd" / "feat_lfp" and "post_sample_csd" / "post_sample_lfp"."""
+        (J, NFEAT, R, nsamples) and, with keep_draws, "csd" / "lfp" (nz, ntstar, R, nsamples) for the requested type -- host arrays,
+        or with resident=True (gpcsd_sample_features_resident) zero-copy views."""
         z, tstar = _sites_times(z, tstar)
         labels = np.ascontiguousarray(labels, dtype=np.int32)
         if labels.shape != (z.shape[0], tstar.size):
             raise ValueError("labels must have shape (%d, %d), not %s" % (z.shape[0], tstar.size, labels.shape))
         xi = None if xi is None else _arr(xi)
         eps = None if eps is None else _arr(eps)
-        args = (self._h, ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size, int(type_code), int(nsamples), int(seed),
+        args = (ctypes.byref(hp), _ptr(z), z.shape[0], _ptr(tstar), tstar.size, int(type_code), int(nsamples), int(seed),
                 _ptr(xi), _ptr(eps), labels.ctypes.data_as(_IP), int(J), int(bool(band)), float(floor), int(bool(keep_draws)))
-        quantities = [(name, buf) for name, bit, buf in (("csd", PRED_CSD, "post_sample_csd"), ("lfp", PRED_LFP, "post_sample_lfp"))
-                      if type_code & bit]
-        fshape = (int(J), NFEAT, int(R) * int(nsamples))
-        dshape = (z.shape[0], tstar.size, int(R), int(nsamples))
-        if resident:
-            self._check(self._lib.gpcsd_sample_features_resident(*args))
-            res = {"feat_" + name: self.device_array("feat_" + name, fshape) for name, _ in quantities}
-            if keep_draws:
-                res.update({name: self.device_array(buf, dshape) for name, buf in quantities})
-            return res
-        res = {"feat_" + name: pinned_pool.empty(fshape) for name, _ in quantities}
-        if keep_draws:
-            res.update({name: pinned_pool.empty(dshape) for name, _ in quantities})
-        self._check(self._lib.gpcsd_sample_features(*args, _ptr(res.get("feat_csd")), _ptr(res.get("feat_lfp")), _ptr(res.get("csd")),
-                                                    _ptr(res.get("lfp"))))
-        return res
+        table = sample_features_outputs(type_code, (z.shape[0], tstar.size, int(R), int(nsamples)), int(J), keep_draws)
+        return _present(self._either_form("sample_features", table, resident, args))
 
     # ---- measurement ----
     def synchronize(self):

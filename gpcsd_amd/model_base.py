@@ -698,8 +698,6 @@ class GPCSDModel:
 
     # ------------------------------------------------------------------ prediction
     _TYPE_CODES = {"csd": _hip.PRED_CSD, "lfp": _hip.PRED_LFP, "both": _hip.PRED_BOTH}
-    _PRED_BUFFERS = (("csd", _hip.PRED_CSD, "pred_out_csd"), ("lfp", _hip.PRED_LFP, "pred_out_lfp"))
-    _VAR_BUFFERS = (("csd", _hip.PRED_CSD, "pred_var_csd"), ("lfp", _hip.PRED_LFP, "pred_var_lfp"))
 
     def _posterior_request(self, z, tstar, type, any_times=False):
         """What every posterior call at sites z and times tstar starts from: (z as float64, its (nz, dim) form, tstar as an array,
@@ -712,17 +710,6 @@ class GPCSDModel:
         if tstar.size < 1 and not any_times:
             raise ValueError("tstar must hold at least one time")
         return z, z2, tstar, self._TYPE_CODES[type]
-
-    def _device_predictions(self, ctx, code, shape, buffers=_PRED_BUFFERS):
-        """Zero-copy views (`_hip.DeviceArray`) of what a resident call left in HBM under `buffers`: per requested quantity the
-        array of `shape` and its "_list" form with a leading axis of the temporal components."""
-        C = len(self.temporal_cov_list)
-        res = {}
-        for name, bit, buf in buffers:
-            if code & bit:
-                res[name] = ctx.device_array(buf, tuple(shape))
-                res[name + "_list"] = ctx.device_array(buf + "_list", (C,) + tuple(shape))
-        return res
 
     def _store_predictions(self, res, z, t):
         if res.get("csd") is not None:
@@ -753,7 +740,7 @@ class GPCSDModel:
         gather = sh is not None and getattr(sh, "gather_predictions", False)
         if resident or (gather and sh.on_device()):
             ctx.predict_resident(hp, z2, t, code, want_lists=True, at=at)
-            res = self._device_predictions(ctx, code, shape)
+            res = ctx.predict_views(code, shape, len(self.temporal_cov_list))
             if gather:
                 # trial blocks gathered ON THE DEVICE (RCCL all-gather over xGMI), one copy out on the gathering rank(s) only
                 res = {k: sh.gather_trials_device(v, dst=getattr(sh, "gather_dst", None)) for k, v in res.items()}
@@ -801,11 +788,7 @@ class GPCSDModel:
         ctx = self._sync_device()
         hp, _keep = self._hparams(0.0)                     # no jitter, as predict
         shape = (z2.shape[0], tstar.size, np.shape(self.lfp)[2])
-        if resident:
-            ctx.predict_masked_resident(hp, mask, z2, tstar, code, want_lists=True)
-            res = self._device_predictions(ctx, code, shape)
-        else:
-            res = ctx.predict_masked(hp, mask, z2, tstar, code, shape)
+        res = ctx.predict_masked(hp, mask, z2, tstar, code, shape, resident=resident)
         self._store_predictions(res, z, tstar)
         return res
 
@@ -843,11 +826,7 @@ class GPCSDModel:
         ctx = self._sync_device()
         hp, _keep = self._hparams(0.0)                     # no jitter, as predict
         C = len(self.temporal_cov_list)
-        if resident:
-            ctx.predict_var_resident(hp, z2, tstar, code)
-            res = self._device_predictions(ctx, code, (z2.shape[0], tstar.size), self._VAR_BUFFERS)
-        else:
-            res = ctx.predict_var(hp, z2, tstar, code)
+        res = ctx.predict_var(hp, z2, tstar, code, resident=resident)
         for name in ("csd", "lfp"):
             if res.get(name) is not None:
                 setattr(self, name + "_var_list", [res[name + "_list"][i] for i in range(C)])
@@ -896,17 +875,8 @@ class GPCSDModel:
                                       "device; only the library's own GPCSDTemporalCov* components are supported")
         ctx = self._sync_device()
         hp, _keep = self._hparams(0.0)                     # no jitter, as predict
-        J, C, R_local = W.shape[0], len(self.temporal_cov_list), self._local_lfp().shape[2]
-        if resident:
-            ctx.predict_functionals_resident(hp, z2, tstar, W, code)
-            raw = {}
-            for name, bit in (("csd", _hip.PRED_CSD), ("lfp", _hip.PRED_LFP)):
-                if code & bit:
-                    for kind, shape in (("mean", (J, R_local)), ("cov", (J, J)), ("prior", (J, J))):
-                        raw["%s_%s" % (name, kind)] = ctx.device_array("fun_%s_%s" % (kind, name), shape)
-                        raw["%s_%s_list" % (name, kind)] = ctx.device_array("fun_%s_%s_list" % (kind, name), (C,) + shape)
-        else:
-            raw = ctx.predict_functionals(hp, z2, tstar, W, code, R_local)
+        C = len(self.temporal_cov_list)
+        raw = ctx.predict_functionals(hp, z2, tstar, W, code, self._local_lfp().shape[2], resident=resident)
         res = {}
         for name in ("csd", "lfp"):
             for kind in ("mean", "cov", "prior"):
@@ -945,18 +915,9 @@ class GPCSDModel:
         counterpart."""
         ctx = self._sync_device()
         hp, _keep = self._hparams(self.JITTER)             # the jitter of loglik
-        nx, nt, R_local = self._local_lfp().shape
-        if resident:
-            ctx.loo_resident(hp, want_mean=mean)
-            self.loo_var = ctx.device_array("loo_var", (nx, nt))
-            self.loo_lpd = ctx.device_array("loo_lpd", (nx, R_local))
-            self.loo_sse = ctx.device_array("loo_sse", (nx, R_local))
-            self.loo_mean = ctx.device_array("loo_mean", (nx, nt, R_local)) if mean else None
-            total = float(np.sum(ctx.fetch("loo_lpd", (nx, R_local))))
-        else:
-            res = ctx.loo(hp, (nx, nt, R_local), want_mean=mean)
-            self.loo_var, self.loo_lpd, self.loo_sse, self.loo_mean = res["var"], res["lpd"], res["sse"], res["mean"]
-            total = float(np.sum(res["lpd"]))
+        res = ctx.loo(hp, self._local_lfp().shape, want_mean=mean, resident=resident)
+        self.loo_var, self.loo_lpd, self.loo_sse, self.loo_mean = res["var"], res["lpd"], res["sse"], res["mean"]
+        total = float(np.sum(res["lpd"].numpy() if resident else res["lpd"]))
         sh = getattr(self, "_sharding", None)
         if sh is not None:
             total = float(sh.allreduce_sum(np.array([total]))[0])
@@ -1051,21 +1012,10 @@ class GPCSDModel:
         ptr, idx = self._fold_arrays(folds, np.atleast_3d(self.lfp).shape[0])
         ctx = self._sync_device()
         hp, _keep = self._hparams(self.JITTER)             # the jitter of loglik
-        nx, nt, R_local = self._local_lfp().shape
-        nf = ptr.size - 1
-        if resident:
-            ctx.cv_electrodes_resident(hp, ptr, idx, want_mean=mean)
-            self.cv_var = ctx.device_array("cv_var", (nx, nt))
-            self.cv_lpd = ctx.device_array("cv_lpd", (nf, R_local))
-            self.cv_sse = ctx.device_array("cv_sse", (nx, R_local))
-            self.cv_mean = ctx.device_array("cv_mean", (nx, nt, R_local)) if mean else None
-            self.cv_status = np.array(ctx.fetch("cv_status", ((nf + 1) // 2,)).view(np.int32)[:nf])
-            lpd = ctx.fetch("cv_lpd", (nf, R_local))
-        else:
-            res = ctx.cv_electrodes(hp, (nx, nt, R_local), ptr, idx, want_mean=mean)
-            self.cv_var, self.cv_lpd, self.cv_sse, self.cv_mean = res["var"], res["lpd"], res["sse"], res["mean"]
-            self.cv_status = res["status"]
-            lpd = res["lpd"]
+        res = ctx.cv_electrodes(hp, self._local_lfp().shape, ptr, idx, want_mean=mean, resident=resident)
+        self.cv_var, self.cv_lpd, self.cv_sse, self.cv_mean = res["var"], res["lpd"], res["sse"], res["mean"]
+        self.cv_status = res["status"]
+        lpd = res["lpd"].numpy() if resident else res["lpd"]
         self.cv_folds = self._fold_tuple(ptr, idx)
         total = float(np.sum(lpd[self.cv_status == 0]))
         sh = getattr(self, "_sharding", None)
@@ -1106,9 +1056,8 @@ class GPCSDModel:
         NotImplementedError.  No reference counterpart."""
         ctx, hp, _keep, ng = self._fisher_args("trial_scores")
         R_local = self._local_lfp().shape[2]
-        if resident:
-            ctx.trial_scores_resident(hp, ng)
-            self.trial_scores_ = ctx.device_array("trial_scores", (R_local, ng))
+        if resident:                                       # this rank's block, where it lies: no gather
+            self.trial_scores_ = ctx.trial_scores(hp, R_local, ng, resident=True)
             return self.trial_scores_
         S = ctx.trial_scores(hp, R_local, ng)
         sh = getattr(self, "_sharding", None)
@@ -1220,7 +1169,7 @@ class GPCSDModel:
                 # overwritten them (one product, no PCIe)
                 keep[name] = {"source": x, "A": A, "generation": ctx.phasor_generation, "shape": tuple(res["u_re"].shape)}
                 if not resident:
-                    res = {k: ctx.fetch(v.name, v.shape) for k, v in res.items() if k in ("phase", "amp")}
+                    res = {k: v.numpy() for k, v in res.items() if k in ("phase", "amp")}
             else:
                 keep[name] = {"u": (res["u_re"], res["u_im"]), "shape": tuple(res["u_re"].shape)}
             setattr(self, name + "_phase", res["phase"])
@@ -1250,7 +1199,7 @@ class GPCSDModel:
                 u = rec["u"]
             else:
                 if rec["generation"] == ctx.phasor_generation:
-                    u = tuple(ctx.device_array(b, rec["shape"]) for b in ("phasor_re", "phasor_im"))
+                    u = ctx.phasors(rec["shape"])
                 else:
                     u = band_phase(rec["source"], rec["A"], want=("u_re", "u_im"), resident=True)
                     rec["generation"] = ctx.phasor_generation
@@ -1371,7 +1320,7 @@ class GPCSDModel:
             if "u" in rec:
                 u = rec["u"]
             elif rec["generation"] == ctx.phasor_generation:
-                u = tuple(ctx.device_array(b, rec["shape"]) for b in ("phasor_re", "phasor_im"))
+                u = ctx.phasors(rec["shape"])
             else:
                 u = band_phase(rec["source"], rec["A"], want=("u_re", "u_im"), resident=True)
                 u = (u["u_re"], u["u_im"])
@@ -1422,18 +1371,16 @@ class GPCSDModel:
                 out[k] = -0.5 * ntrials * sumlog - 0.5 * quad
         finally:
             ctx.pair_share_s(was)
-        res = self._device_predictions(ctx, code, (z2.shape[0], t.shape[0], R_local))
+        res = ctx.predict_views(code, (z2.shape[0], t.shape[0], R_local), len(self.temporal_cov_list))
         gather = sh is not None and getattr(sh, "gather_predictions", False)
         if gather and sh.on_device():
             res = {k: sh.gather_trials_device(v, dst=getattr(sh, "gather_dst", None)) for k, v in res.items()}
         elif not resident or gather:
-            res = {k: ctx.fetch(v.name, v.shape) for k, v in res.items()}
+            res = {k: v.numpy() for k, v in res.items()}
             if gather:
                 res = {k: sh.gather_trials(v) for k, v in res.items()}
         self._store_predictions(res, z, t)
         return out
-
-    _SAMPLE_BUFFERS = (("csd", _hip.PRED_CSD, "post_sample_csd"), ("lfp", _hip.PRED_LFP, "post_sample_lfp"))
 
     def _sample_posterior_args(self, z, tstar, type, nsamples):
         """Validation and shapes shared by sample_posterior and _sample_posterior_from_normals; opens no context."""
@@ -1455,9 +1402,6 @@ class GPCSDModel:
         # a rank's block of trials draws the normals the unsharded job draws for those trials
         ctx.set_trial_offset(0 if sh is None else sh.local_slice(np.atleast_3d(self.lfp).shape[2]).start or 0)
         res = ctx.sample_posterior(hp, z2, tstar, code, nsamples, seed, R_local, xi=xi, eps=eps, resident=resident)
-        if resident:
-            shape = (z2.shape[0], tstar.size, R_local, int(nsamples))
-            res = {name: ctx.device_array(buf, shape) for name, bit, buf in self._SAMPLE_BUFFERS if code & bit}
         return res.get("csd"), res.get("lfp")
 
     def sample_posterior(self, z, tstar, nsamples=1, type="csd", seed=1, resident=False):
@@ -1512,9 +1456,7 @@ class GPCSDModel:
         feats = []
         for name in ("csd", "lfp"):
             f = res.get("feat_" + name)
-            if f is not None and resident:
-                f = _hip.DeviceArray(f.ptr, (J, _hip.NFEAT, R_local, nsamples), ctx, f.name)
-            elif f is not None:
+            if f is not None and not resident:
                 f = features_from_slots(f, (R_local, nsamples), tstar.reshape(-1).astype(np.float64), np.asarray(z2, dtype=np.float64), band)
             feats.append(f)
         if return_draws:

@@ -217,7 +217,7 @@ def region_features(x, labels, tstar=None, z=None, mean=None, isd=None, resident
         view = ctx.region_features_resident(x.base[0], x.base[1], (nz, n, M), labels, J, tstar, z, mean, isd, S)
         if resident:
             return {"feat": _hip.DeviceArray(view.ptr, (J, _hip.NFEAT) + shape[2:], ctx, view.name)}
-        feat = ctx.fetch(view.name, view.shape)
+        feat = view.numpy()
     else:
         if resident:
             raise ValueError("resident=True needs a device input")
